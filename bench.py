@@ -6,21 +6,28 @@ dissector chain kernel over the batch (records + ext + per-protocol counters)
 plus, for N > 1 GPUs, the RCCL all-reduce of the counter vector.  Records
 are the compact 8-byte form by default (nsd_crec: ops ids, IPv4 checksum,
 flags; the renderer re-derives the cursors), --records full
-times the 16-byte nsd_rec; the other form is measured beside it
-("other_records").
+times the 16-byte nsd_rec.
 --config imix / ipv6x select C3 / C4 as the headline instead; --shards S
 walks S contiguous 16M shards of the same stream as one batch on one GPU
 (--config imix --shards 8 = C5's 128M packets on a single MI355X).
 
-At every N (rank r walks its own 16M-packet shard [r * 16M, (r + 1) * 16M)
-of each config; the counter vector is all-reduced over the ranks inside the
-timed region and checked against the oracle's per-shard counters,
-tests/golden/shard_counters.json):
-  headline    C2 (or --config), `value` = whole-job Mpkt/s, per-GPU roofline;
+A plain run does what the headline needs and no more: it generates and
+uploads the batch, warms up, times exactly --steps launches and prints the
+line (`value` = whole-job Mpkt/s, `ms_per_step`, the roofline of the timed
+launches' own kernel time).  Rank r walks its own 16M-packet shard
+[r * 16M, (r + 1) * 16M); the counter vector is all-reduced over the ranks
+inside the timed region and checked against the oracle's per-shard counters
+(tests/golden/shard_counters.json).  --dump-outputs DIR then writes what the
+last timed launch left in the caller's buffers (dump_outputs).
+
+--full adds, at every N:
   legs        C3 IMIX (the metric is "64B & IMIX"; at N = 8 its shards are
               C5's 128M IMIX packets across 8 GPUs) and C4, each with its
               whole-job rate, per-GPU kernel time and roofline.
-Beside them, at N = 1 only:
+and, at N = 1 only:
+  ceilings    a device-to-device copy's rate and the read-only ceiling
+              (tools/bw) over the resident frames, beside the spec peak in
+              every roofline;
   traffic     HBM bytes per launch from rocprofv3 PMC counters, collected
               in-run by two child processes (FETCH_SIZE and WRITE_SIZE in
               separate passes, MI355X_MICROARCH.md "HBM") before this
@@ -33,9 +40,9 @@ Beside them, at N = 1 only:
               as one process per core of the 16-CPU share, C2 and C3;
   end_to_end / replay / bpf_filter (reported, never `value`).
 
-Launch: python bench.py [--gpus N --steps K --warmup W]; for N > 1 under
-torch.distributed.run (one rank per GPU, weak scaling: every rank walks its
-own 16M-packet shard).  Rank 0 prints one JSON line.
+Launch: python bench.py [--gpus N --steps K --warmup W] [--full]; for N > 1
+under torch.distributed.run (one rank per GPU, weak scaling: every rank
+walks its own 16M-packet shard).  Rank 0 prints one JSON line.
 """
 import argparse
 import ctypes
@@ -896,6 +903,70 @@ def measure_rank(args, rank, world, dev, engine="device"):
 
 
 
+DUMP_RECORDS = 1 << 19   # records in a dump's sample (a batch up to this size is dumped whole)
+DUMP_SEED = 0xD0B5
+
+
+def dump_outputs(path, b, m, rank, world):
+    """--dump-outputs: what the timed launches left in the caller's buffers
+    after the last of them, as float64 <name>.npy files under `path`
+    (<name>_rank<r>.npy for N > 1: every rank dumps its own shard), so that
+    two builds run with the same arguments compare array for array (the
+    inputs are seeded: T.SEED):
+      counters      the 64-word counter vector as the timed region returns it:
+                    accumulated over the launches when they run back to back
+                    (the line's counters_total), all-reduced over the ranks;
+      ext_used      the ext-pool words handed out;
+      record_index  the sampled packets: all of a batch of up to DUMP_RECORDS
+                    packets, else a fixed seeded sample of them, ascending;
+      records       one row per sampled packet, the record's fields in
+                    declaration order (nsd_crec: chain, ip_csum, nflags,
+                    nlayers, then its side word, 0 where the record has none;
+                    nsd_rec: chain, data_off, tail_off, ip_csum, nflags,
+                    off2[0..4]), then ext_nlayers.  A record in ext-entry form
+                    names a pool slot, which depends on the order the waves
+                    took pool words in: its slot field is dumped as -1 and
+                    ext_nlayers holds the entry's layer count (else 0).
+    The host engine has no record buffers: counters only."""
+    os.makedirs(path, exist_ok=True)
+    tag = "" if world == 1 else f"_rank{rank}"
+    out = {"counters": m["counters"].astype(np.float64)}
+    if getattr(b, "rec", None) is not None:
+        n = b.n
+        if n <= DUMP_RECORDS:
+            idx = np.arange(n, dtype=np.int64)
+        else:
+            idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, n, DUMP_RECORDS, dtype=np.int64))
+        it = torch.from_numpy(idx).to(b.rec.device)
+        rec = b.rec.view(n, b.rec_b)[it].cpu().numpy().reshape(-1)
+        rec = rec.view(nsd.CREC_DTYPE if b.compact else nsd.REC_DTYPE)
+        ext_form = ((rec["nflags"] & 7) == 7) & ((rec["nflags"] & nsd.F_OVERFLOW) == 0)
+        if b.compact:
+            side = b.ext[it].cpu().numpy().view(np.uint32)
+            ext_form &= rec["nlayers"] == 0
+            has_side = (rec["nlayers"] != 0) | (((rec["nflags"] & 7) != 7) & ((rec["nflags"] & nsd.F_LEAF_END) != 0))
+            cols = [rec["chain"], rec["ip_csum"], rec["nflags"], rec["nlayers"], np.where(has_side, side, 0)]
+            slot, slot_col = rec["chain"].astype(np.int64), 0
+        else:
+            cols = [rec["chain"], rec["data_off"], rec["tail_off"], rec["ip_csum"], rec["nflags"]]
+            cols += [rec["off2"][:, k] for k in range(5)]
+            slot, slot_col = rec["off2"][:, :4].copy().view("<u4").reshape(-1).astype(np.int64), None
+        nl = np.zeros(len(rec), dtype=np.float64)
+        ok = ext_form & (slot != 0xFFFFFFFF)
+        if ok.any():
+            at = torch.from_numpy(np.minimum(slot[ok] + 1, b.ext.numel() - 1)).to(b.rec.device)
+            nl[ok] = b.ext[at].cpu().numpy().view(np.uint32) & 0xFFFF
+        rows = np.stack([np.asarray(c, dtype=np.float64) for c in cols] + [nl], axis=1)
+        if slot_col is None:
+            rows[ext_form, 5:9] = -1
+        else:
+            rows[ext_form, slot_col] = -1
+        out.update(records=rows, record_index=idx.astype(np.float64),
+                   ext_used=np.array([int(b.ext_used.item())], dtype=np.float64))
+    for name, a in out.items():
+        np.save(os.path.join(path, f"{name}{tag}.npy"), a)
+
+
 SHARD_COUNTERS = os.path.join(ROOT, "tests", "golden", "shard_counters.json")
 
 
@@ -965,6 +1036,12 @@ def parse_args(argv=None):
     ap.add_argument("--grid", type=int, default=0)
     ap.add_argument("--records", default="compact", choices=["compact", "full"],
                     help="record form of the timed launches: 8-byte nsd_crec or 16-byte nsd_rec")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: the C3 / C4 legs, the other record form, PMC traffic, "
+                         "copy rate and read ceiling, CPU baseline, end to end, replay and BPF (the --no-* "
+                         "switches below take single ones out again)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step left in the caller's buffers as DIR/<name>.npy")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=24.0, help="CPU baseline duration (all legs)")
     ap.add_argument("--no-e2e", action="store_true", help="skip the host-memory end-to-end pass")
@@ -982,16 +1059,21 @@ def parse_args(argv=None):
     # way, through spawn_ranks and torch.distributed.run); never a bench run
     ap.add_argument("--engine", default="device", choices=["device", "host"], help=argparse.SUPPRESS)
     ap.add_argument("--pmc-configs", default="", help=argparse.SUPPRESS)
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if not args.full:
+        # a plain run: set up, warm up, time the steps, print the line
+        args.no_cpu = args.no_e2e = args.no_bpf = args.no_replay = args.no_legs = args.no_pmc = True
+    return args
 
 
 def run(args, rank, world, dev, engine="device", traffic=None):
     """Every rank's measurements in launch order (the same collectives on
     every rank), and rank 0's JSON line (a dict; None on other ranks).  At
-    every N: the headline workload and each leg (C3 IMIX, whose 8-rank run is
-    C5, and C4) through measure_rank, the counters all-reduced and checked
-    against the oracle's per-shard counters.  N = 1 only: the other record
-    form, the CPU baseline, end to end, replay and BPF.  engine "host"
+    every N: the headline workload through measure_rank, the counters
+    all-reduced and checked against the oracle's per-shard counters.  With
+    --full, at every N: each leg (C3 IMIX, whose 8-rank run is C5, and C4)
+    the same way; N = 1 only: the copy rate and read ceiling, the other
+    record form, the CPU baseline, end to end, replay and BPF.  engine "host"
     (tests/test_multi.py) walks each shard with the product's host walk and
     skips the device-only legs."""
     solo = rank == 0 and world == 1
@@ -1006,8 +1088,11 @@ def run(args, rank, world, dev, engine="device", traffic=None):
     ms_per_step = elapsed / args.steps * 1e3
     mpps = total_pkts * args.steps / elapsed / 1e6
 
-    copy_gbs = copy_rate(dev) if dev_eng else None
-    ceiling = read_ceiling(b.frames) if dev_eng else None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, b, m, rank, world)
+
+    copy_gbs = copy_rate(dev) if dev_eng and args.full else None
+    ceiling = read_ceiling(b.frames) if dev_eng and args.full else None
     head = workload_result(args, args.config, b, m, world, engine, traffic, copy_gbs, ceiling)
     roofline = head["roofline"]
     # the BPF leg filters C3's IMIX (its "IPv4 TCP" program accepts the

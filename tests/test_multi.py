@@ -66,7 +66,8 @@ def _run_worker(rank, world, port, per_rank, steps, out):
     import bench
     nsd_dist.init("gloo")
     r, w, _ = nsd_dist.rank_env()
-    args = bench.parse_args(["--gpus", str(w), "--packets", str(per_rank), "--steps", str(steps), "--warmup", "1"])
+    args = bench.parse_args(["--gpus", str(w), "--packets", str(per_rank), "--steps", str(steps), "--warmup", "1",
+                             "--full"])
     line = bench.run(args, r, w, "cpu", engine="host")
     assert (line is None) == (r != 0)
     if r == 0:
@@ -118,7 +119,7 @@ def test_bench_cli_n_ranks():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--engine", "host",
-                        "--packets", str(per_rank), "--steps", str(steps), "--warmup", "1", "--no-pmc"],
+                        "--packets", str(per_rank), "--steps", str(steps), "--warmup", "1", "--full", "--no-pmc"],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert r.returncode == 0, r.stderr.decode(errors="replace")[-2000:]
     lines = [ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")]
@@ -217,7 +218,7 @@ def _nccl_worker(rank, world, port, per_rank, steps, out):
     dist.all_reduce = counted
     try:
         args = bench.parse_args(["--gpus", "1", "--packets", str(per_rank), "--steps", str(steps), "--warmup", "1",
-                                 "--no-cpu", "--no-e2e", "--no-replay", "--no-bpf", "--no-pmc"])
+                                 "--full", "--no-cpu", "--no-e2e", "--no-replay", "--no-bpf", "--no-pmc"])
         line = bench.run(args, 0, 1, torch.device("cuda", 0), "device")
     finally:
         dist.all_reduce = real

@@ -16,7 +16,7 @@ if [ -n "$TESTS" ]; then
   echo "pytest rc=$rc"; tail -n 15 "$O/pytest_gpu.log"; fatal $rc pytest
 fi
 for cfg in ${CFGS-udp64 imix ipv6x}; do
-  timeout -k 10 600 python bench.py --config $cfg --steps 10 --warmup 2 --no-cpu --no-e2e ${BENCH_ARGS} > "$O/bench_$cfg.log" 2>&1; rc=$?
+  timeout -k 10 600 python bench.py --full --config $cfg --steps 10 --warmup 2 --no-cpu --no-e2e ${BENCH_ARGS} > "$O/bench_$cfg.log" 2>&1; rc=$?
   echo "bench $cfg rc=$rc"
   python3 - "$O/bench_$cfg.log" <<'EOF' || tail -5 "$O/bench_$cfg.log"
 import json, sys
@@ -28,7 +28,7 @@ EOF
 done
 cd /tmp && export TMPDIR=/tmp
 for cfg in $PROF; do
-  timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$O/prof_$cfg" -o run --output-format csv -- python3 "$R/bench.py" --config $cfg --steps 5 --warmup 1 --no-cpu --no-e2e > "$O/prof_$cfg.log" 2>&1; rc=$?
+  timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$O/prof_$cfg" -o run --output-format csv -- python3 "$R/bench.py" --full --config $cfg --steps 5 --warmup 1 --no-cpu --no-e2e > "$O/prof_$cfg.log" 2>&1; rc=$?
   echo "prof $cfg rc=$rc"; fatal $rc prof
   f=$(find "$O/prof_$cfg" -name '*kernel_stats.csv' | head -n 1)
   python3 - "$f" <<'EOF'

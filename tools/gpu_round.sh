@@ -17,11 +17,11 @@ if [ -z "$NO_TESTS" ]; then
   timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > "$O/smoke.log" 2>&1; rc=$?
   echo "smoke rc=$rc"; tail -n 2 "$O/smoke.log"; fatal $rc smoke
 fi
-timeout -k 10 900 python -u bench.py > "$O/bench_default.log" 2> "$O/bench_default.err"; rc=$?
+timeout -k 10 900 python -u bench.py --full > "$O/bench_default.log" 2> "$O/bench_default.err"; rc=$?
 echo "bench default rc=$rc"; tail -c 600 "$O/bench_default.log"; echo; fatal $rc bench
-timeout -k 10 900 python -u bench.py --config imix --shards 8 --no-cpu --no-e2e --no-replay --no-bpf --no-legs --steps 5 --warmup 1 > "$O/bench_c5.log" 2> "$O/bench_c5.err"; rc=$?
+timeout -k 10 900 python -u bench.py --full --config imix --shards 8 --no-cpu --no-e2e --no-replay --no-bpf --no-legs --steps 5 --warmup 1 > "$O/bench_c5.log" 2> "$O/bench_c5.err"; rc=$?
 echo "bench c5 rc=$rc"; tail -c 300 "$O/bench_c5.log"; echo; fatal $rc bench_c5
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$O/stats" -o run --output-format csv -- python3 "$R/bench.py" --no-cpu --no-e2e --no-replay --no-pmc --steps 10 --warmup 2 > "$O/stats.log" 2>&1; rc=$?
+timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$O/stats" -o run --output-format csv -- python3 "$R/bench.py" --full --no-cpu --no-e2e --no-replay --no-pmc --steps 10 --warmup 2 > "$O/stats.log" 2>&1; rc=$?
 echo "stats rc=$rc"; fatal $rc stats
 exit 0

@@ -2,7 +2,7 @@
 # One GPU session (run under gpurun from the repo root): optional parity
 # tests, then bench lines, each GPU step under its own time limit; a fault,
 # abort or timeout ends the script.  Outputs in gpurun_out/$TAG/.
-#   TAG=r02a TESTS=1 PYTEST_ARGS="-k c5" BENCH1="" BENCH2="--config imix --shards 8 --no-cpu"
+#   TAG=r02a TESTS=1 PYTEST_ARGS="-k c5" BENCH1="--full" BENCH2="--full --config imix --shards 8 --no-cpu"
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" || exit 1
 R=$(pwd)
 O=$R/gpurun_out/${TAG:-session}
