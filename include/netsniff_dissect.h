@@ -443,10 +443,12 @@ long nsd_format_batch_compact(const uint8_t *frames, const nsd_desc_t *desc, con
 			      const uint32_t *ext_pool, char *out, size_t cap, uint64_t *ends,
 			      int8_t *rc);
 
-/* Kernel schedule of the batch walks.  NSD_SCHED_SPLIT: a fast kernel
- * (fast walk of every packet at high occupancy) plus a walker kernel over
- * the packets it defers; NSD_SCHED_FUSED: one kernel doing both; results
- * are identical.  NSD_SCHED_ADAPTIVE (the default) picks per device from the
+/* Kernel schedule of the batch walks, one launch either way.
+ * NSD_SCHED_SPLIT: a kernel that first runs the fast walk of every packet
+ * (two tiles of frames in flight per wave), each block then walking the
+ * packets its waves deferred; NSD_SCHED_FUSED: a kernel whose waves walk a
+ * tile's deferred packets right after its fast walk; results are
+ * identical.  NSD_SCHED_ADAPTIVE (the default) picks per device from the
  * recently observed share of deferred packets (split for traffic the fast
  * walk finishes, fused for deep chains).  nsd_set_schedule returns the
  * previous setting (or NSD_ERR_ARG); nsd_last_schedule the schedule of the

@@ -25,6 +25,11 @@
 // per-lane windows staged at each walker's cursor, idle walkers refilled,
 // ext spill; ICMPv4 payload checksums longer than a window are summed by the
 // block at the end.
+//
+// One launch per batch, in one of two schedules (the launcher picks, see
+// "the schedule"): fused (dissect_all: a tile's walkers right after its fast
+// walk) or split (dissect_fast: the fast walk of every tile first, deferred
+// packets listed per wave, then each wave walks its own list).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -39,28 +44,15 @@ namespace nsd {
 constexpr int BLOCK = 256;
 constexpr int WAVES = BLOCK / 64;
 
-// Summed over launches on this device and sampled now and then by the
-// launcher to choose the schedule (split or fused, nsd_launch_dissect_rec):
-// [0] packets the fast walk handed to the general walk, [1] ICMPv4 messages
-// left to a checksum pass (longer than their window)
-constexpr int WIN1 = 64;         // bytes per staged window, pass 1
+// ---- numeric tunables (each overridable with -D: tools/build_variant.sh) -----
 #ifndef NSD_WIN2
-#define NSD_WIN2 128
+#define NSD_WIN2 128               // bytes per staged window of the general walk's continuation
 #endif
-constexpr int WIN2 = NSD_WIN2;   // bytes per staged window, general-walk continuation
-// fast-walk window row stride in dwords (16-byte aligned rows, see top)
-constexpr int row_of(int W) { return W / 4 + 4; }
 #ifndef NSD_CSUM_U
 #define NSD_CSUM_U 12              // interior chunk loads in flight per lane (icmp_pass)
 #endif
-#ifndef NSD_GROUP_TILES
-#define NSD_GROUP_TILES 1          // fused waves take their tiles at run time from a counter per CU group
-#endif
-#ifndef NSD_GROUP_BLOCKS
-#define NSD_GROUP_BLOCKS 4u        // blocks sharing a tile counter (4: one CU's; 8: two CUs of one XCD)
-#endif
-#ifndef NSD_PRIO
-#define NSD_PRIO 1                 // fused waves' issue priority by their tile progress (walk_tiles)
+#ifndef NSD_FAST_CSUM_U
+#define NSD_FAST_CSUM_U 8          // the same in fast_icmp_pass (4: C3 split +4 %)
 #endif
 #ifndef NSD_CSUM_LANES
 #define NSD_CSUM_LANES 8           // lanes per message in icmp_pass (each group instruction: 8 = one 128-B line)
@@ -68,24 +60,41 @@ constexpr int row_of(int W) { return W / 4 + 4; }
 #ifndef NSD_MINW
 #define NSD_MINW 4                 // waves per SIMD the fused kernel is register-allocated for
 #endif
+#ifndef NSD_FAST_MINW
+#define NSD_FAST_MINW 4            // waves per SIMD dissect_fast is register-allocated for (compact records)
+#endif
+#ifndef NSD_FAST_MINW_FULL
+#define NSD_FAST_MINW_FULL 4       // the same for 16-byte records (the deferral entries carry layer starts)
+#endif
+#ifndef NSD_FAST_BPC
+#define NSD_FAST_BPC 3             // resident fast blocks per CU (0: as many as fit)
+#endif
+#ifndef NSD_FAST_BPC_SMALL
+#define NSD_FAST_BPC_SMALL 2       // the same when the sampled frames average at most NSD_SMALL_FRAME bytes
+#endif
+#ifndef NSD_GROUP_BLOCKS
+#define NSD_GROUP_BLOCKS 4u        // blocks sharing a tile counter (4: one CU's; 8: two CUs of one XCD)
+#endif
 #ifndef NSD_L2PF
-#define NSD_L2PF 16                // a tile with this many deferred packets is walker-heavy (NSD_LATE)
+#define NSD_L2PF 16                // a tile with this many deferred packets is walker-heavy (walk_tiles' `late`)
 #endif
-#ifndef NSD_LATE
-#define NSD_LATE 1                 // a walker-heavy tile's successor loads its chunks after the walkers (0: before, with L2 touches)
+#ifndef NSD_REFILL
+#define NSD_REFILL 16              // idle walkers at which a session stops to take waiting packets (walkers)
 #endif
-#ifndef NSD_FAST_EXT
-#define NSD_FAST_EXT 1             // the fused kernel's fast walk steps extension headers in its window
+#ifndef NSD_WIN_AHEAD
+#define NSD_WIN_AHEAD 32           // bytes a walker's window keeps past the next layer's in its last line (window_len)
 #endif
-#ifndef NSD_WIN_NT
-#define NSD_WIN_NT 1               // the walkers' window loads nontemporal (stage_glds)
+#ifndef NSD_SCHED_SAMPLE
+#define NSD_SCHED_SAMPLE 32        // launches on a device between two schedule samples (sched_plan)
 #endif
-#ifndef NSD_RING
-#define NSD_RING 1                 // the fused kernel's compact records through the per-wave record ring (RingSt)
+#ifndef NSD_SMALL_FRAME
+#define NSD_SMALL_FRAME 128        // average frame bytes up to which a sampled batch counts as small frames
 #endif
-#ifndef NSD_CSUM_SPLIT
-#define NSD_CSUM_SPLIT 1           // dissect_icmp blocks per pass-1 block
-#endif
+
+constexpr int WIN1 = 64;         // bytes per staged window, pass 1
+constexpr int WIN2 = NSD_WIN2;   // bytes per staged window, general-walk continuation
+// fast-walk window row stride in dwords (16-byte aligned rows, see top)
+constexpr int row_of(int W) { return W / 4 + 4; }
 
 typedef uint32_t v4u __attribute__((ext_vector_type(4)));
 // a chunk in global memory: an address rebuilt from shuffled integers is a
@@ -372,7 +381,7 @@ __device__ __forceinline__ void stage_write(uint32_t *wwin, const Chunks<WIN> &c
 // the banks (dword j of row q at j ^ (swz(q) << 2)).  No VGPR holds the
 // window on the way.  Chunks wholly past the frame are not loaded (the
 // source masks the bytes past caplen instead).  The loads are nontemporal
-// (NSD_WIN_NT): a window's lines are read once, and as L2-allocating loads
+// (aux 2): a window's lines are read once, and as L2-allocating loads
 // they pushed out the packets' first lines that the late chunk loads had
 // just brought in for the walkers (C4: 308.6 -> 259.4 B/packet read, 40.5M
 // -> 34.0M 128-byte requests per launch against a line floor of 262.9;
@@ -398,27 +407,11 @@ __device__ __forceinline__ void stage_glds(uint32_t *wwin, uint64_t abase, uint3
 			const uint64_t a = ((uint64_t)(ahr & 0xFFFFu) << 32 | alo) + 16 * c;
 			__builtin_amdgcn_global_load_lds((const void *)a,
 							 (__attribute__((address_space(3))) void *)(wwin + r * 256), 16, 0,
-							 NSD_WIN_NT ? 2 : 0);
+							 2);
 		}
 	}
 	// the DMA's LDS writes are ordered for this wave's reads by its vmcnt only
 	asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-}
-
-// Touch the first line(s) of a packet's fast window so a later load of it
-// hits L2: one 4-byte LDS-DMA load per line (64 lanes write 256 bytes of
-// `dummy`, an LDS area nothing reads, so no VGPR waits for the line).  Both
-// lines when the window straddles a 128-byte line.
-__device__ __forceinline__ void l2_touch(const uint8_t *frames, uint64_t d, uint32_t *dummy, bool on)
-{
-	const uint64_t a = (uint64_t)frames + NSD_DESC_OFF(d);
-	const uint32_t span = NSD_DESC_CAPLEN(d) < 64 ? (uint32_t)NSD_DESC_CAPLEN(d) : 64u;
-	if (on)
-		__builtin_amdgcn_global_load_lds((const void *)(a & ~127ull),
-						 (__attribute__((address_space(3))) void *)dummy, 4, 0, 0);
-	if (on && (a & 127) + span > 128)
-		__builtin_amdgcn_global_load_lds((const void *)((a & ~127ull) + 128),
-						 (__attribute__((address_space(3))) void *)dummy, 4, 0, 0);
 }
 
 __device__ __forceinline__ void wave_sync_lds()
@@ -506,7 +499,7 @@ __device__ __forceinline__ void put_rec(void *rec, uint32_t i, const WalkOut &w)
 }
 
 // The fused tile loop's pending-list entries and, without the record ring
-// (NSD_RING 0: r05's schedule), its compact records, held one tile: a
+// (the plain build, RING false), its compact records, held one tile: a
 // tile's stores are issued after the next tile's
 // chunk wait and before its prefetch loads, so the wait that precedes each
 // tile (vmcnt(0): its chunks are the youngest loads) finds them issued a
@@ -551,8 +544,8 @@ struct HeldSt {
 	}
 };
 
-// The split fast loop's stores.  With NSD_FAST_ASMST they are inline-asm
-// vector stores: hipcc's waitcnt pass treats the vector-memory counter as
+// The split fast loop's stores are inline-asm vector stores: hipcc's
+// waitcnt pass treats the vector-memory counter as
 // out of order while loads and stores are both pending and then waits
 // vmcnt(0) for a tile's chunks - for every later chunk load and every store
 // too, which defeats a deeper prefetch.  It does not see these stores, so its
@@ -568,41 +561,25 @@ struct HeldSt {
 // than 8 bytes reads its data registers over two cycles, and hipcc's hazard
 // recognizer does not know an asm statement is such a store: the next VALU
 // could overwrite the data before it is read (gfx9's 12-dword store hazard;
-// without the wait state a depth-3 build wrote corrupt list entries and
-// faulted the GPU).  The 16-byte forms end in s_nop 1.
-#ifndef NSD_FAST_DEPTH
-#define NSD_FAST_DEPTH 2           // tiles of chunks in flight per fast wave (1..3)
-#endif
-#ifndef NSD_FAST_ASMST
-#define NSD_FAST_ASMST (NSD_FAST_DEPTH > 1)
-#endif
+// without the wait state a build with three tiles in flight wrote corrupt
+// list entries and faulted the GPU).  The 16-byte forms end in s_nop 1.
 __device__ __forceinline__ void st_b32(uint32_t *p, uint32_t v)
 {
-	if (NSD_FAST_ASMST)
-		asm volatile("global_store_dword %0, %1, off" ::"v"(p), "v"(v) : "memory");
-	else
-		*p = v;
+	asm volatile("global_store_dword %0, %1, off" ::"v"(p), "v"(v) : "memory");
 }
 __device__ __forceinline__ void st_b128(uint4 *p, uint4 x)
 {
-	if (NSD_FAST_ASMST) {
-		const v4u v = { x.x, x.y, x.z, x.w };
-		asm volatile("global_store_dwordx4 %0, %1, off\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
-	} else {
-		*p = x;
-	}
+	const v4u v = { x.x, x.y, x.z, x.w };
+	asm volatile("global_store_dwordx4 %0, %1, off\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
 }
 __device__ __forceinline__ void drain_stores()
 {
-	if (NSD_FAST_ASMST)
-		asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+	asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 template <bool CR>
 __device__ __forceinline__ void put_rec_st(void *rec, uint32_t i, const WalkOut &w)
 {
-	if (!NSD_FAST_ASMST) {
-		put_rec<CR>(rec, i, w);
-	} else if constexpr (CR) {
+	if constexpr (CR) {
 		const uint2 r = crec_of(w);
 		const v2u v = { r.x, r.y };
 		asm volatile("global_store_dwordx2 %0, %1, off sc1" ::"v"((v2u *)rec + i), "v"(v) : "memory");
@@ -962,9 +939,6 @@ __device__ __forceinline__ void emit_general(Shared &sh, RingSt &rs, bool fin, W
 // costs one window wait (1.15 sessions per C4 tile against 2 rounds) and
 // its steps run with refilled lanes (7.2 layer steps per C4 tile against 9.8
 // when each tile's deferred lanes are walked to their ends).
-#ifndef NSD_REFILL
-#define NSD_REFILL 16   // idle walkers at which a session stops to take waiting packets
-#endif
 struct Walker {
 	WalkOut w;
 	uint64_t d;       // its packet's descriptor
@@ -1013,16 +987,8 @@ __device__ __forceinline__ void ring_turn(Shared &sh, RingSt &rs, const Walker &
 // stages nothing.  C4 (line model over the oracle's layer starts): 1.09
 // staged windows per packet against 0.93, 233 against 279 distinct bytes
 // per packet.
-#ifndef NSD_WIN_LINES
-#define NSD_WIN_LINES 1
-#endif
-#ifndef NSD_WIN_AHEAD
-#define NSD_WIN_AHEAD 32
-#endif
 __device__ __forceinline__ uint32_t window_len(uint64_t abs_wb, uint64_t abs_cur, uint32_t need)
 {
-	if (!NSD_WIN_LINES)
-		return WIN2;
 	if (!need)
 		return 0;
 	uint64_t le = ((abs_cur + need - 1) | 127) + 1;
@@ -1338,7 +1304,7 @@ __device__ __forceinline__ void walk_tiles(Shared &sh, const uint8_t *__restrict
 	// while its tiles are left.  Grids that are not 4 blocks per CU share
 	// per block.  Compact records only (the 16-byte form's walk state leaves
 	// no registers for it: 12 VGPRs spilled).
-	constexpr bool DYN = NSD_GROUP_TILES && CR;
+	constexpr bool DYN = CR;
 	const uint32_t ntiles = (n + 63) / 64;
 	const uint32_t nw = gridDim.x * WAVES;
 	const bool grp4 = gridDim.x % NSD_GROUP_BLOCKS == 0;
@@ -1398,7 +1364,7 @@ __device__ __forceinline__ void walk_tiles(Shared &sh, const uint8_t *__restrict
 	wk.stage = false;
 
 	// late: the next tile's chunks load after this tile's walkers (this tile's
-	// predecessor was walker-heavy: NSD_LATE, below)
+	// predecessor was walker-heavy, below)
 	bool late = false;
 	HeldSt<CR> hs;   // the previous tile's record / pending-list stores
 	hs.ri = hs.pp = 0xFFFFFFFFu;
@@ -1413,7 +1379,7 @@ __device__ __forceinline__ void walk_tiles(Shared &sh, const uint8_t *__restrict
 	const uint32_t share = (ntiles + nw - 1) / nw;
 	uint32_t done = 0, lvl = 0xFFu;
 	for (;;) {
-		if (NSD_PRIO && CR && prio) {   // (the 16-byte form's walk state leaves no registers for it)
+		if (CR && prio) {   // (the 16-byte form's walk state leaves no registers for it)
 			const uint32_t l = done < share ? 4u * done / share : 3u;
 			if (l != lvl) {
 				lvl = l;
@@ -1452,7 +1418,7 @@ __device__ __forceinline__ void walk_tiles(Shared &sh, const uint8_t *__restrict
 			const LSrc<true, WIN1> src{ &s_win[wv][lane * ROW], s_lay3, nullptr, frames + off, caplen,
 						    (uint32_t)off & 15, 0, false };
 			if (valid)
-				fw = fast_walk<MODE, false, NSD_FAST_EXT != 0>(src, caplen, w);
+				fw = fast_walk<MODE, false, true>(src, caplen, w);
 			deferred = fw != FW_DONE;
 			ndefer += FlagCnt::pc(deferred);
 			wave_sync_lds();
@@ -1554,18 +1520,7 @@ __device__ __forceinline__ void walk_tiles(Shared &sh, const uint8_t *__restrict
 		// registers are dead during the walkers either way.
 		if (late && (DYN ? nb1 : base + stride) < n)
 			stage_load<WIN1, false, false>(ch, frames, d1, lane);
-		// (NSD_LATE 0: the chunks load a tile ahead, and while the walkers are
-		// busy the lines of tile t+2 go into L2 now, so the next iteration's
-		// loads of them wait for L2 rather than HBM: C4 1.45 -> 1.32 ms then.
-		// Not for tiles the fast walk finishes (C2, C3): there the next loads
-		// would wait for the touches (vector memory counts in order; C2
-		// +12 %).  The LDS-DMA target is window words past the fast rows.)
-		{
-			const uint32_t b2 = DYN ? nb2 : base + 2 * stride;
-			if (!NSD_LATE && many && b2 < n)
-				l2_touch(frames, d2, &s_win[wv][64 * ROW], b2 + lane < n);
-		}
-		late = NSD_LATE && many;
+		late = many;
 		d0 = d1;
 		d1 = d2;
 		if constexpr (DYN) {
@@ -1576,7 +1531,7 @@ __device__ __forceinline__ void walk_tiles(Shared &sh, const uint8_t *__restrict
 			base += stride;
 		}
 	}
-	if (NSD_PRIO && CR && prio)
+	if (CR && prio)
 		__builtin_amdgcn_s_setprio(0);   // the leaf and checksum passes at the neutral level
 	fc.flush(s_cnt, lane);
 	// the pending list held every entry (ask()'s room rule: a packet adds at
@@ -1692,14 +1647,17 @@ __global__ __launch_bounds__(BLOCK, NSD_MINW) void dissect_all(
 
 
 // ==== the split schedule ===========================================================
-// Two launches per batch.  dissect_fast runs the fast walk of every tile at
-// high occupancy (8 waves per SIMD: its registers and LDS are only what the
-// fast walk needs), writes the records of the packets it finishes, sums the
-// ICMPv4 messages they leave pending and appends every packet it cannot
-// finish to its wave's deferral list; dissect_walk runs the walker pool
-// (walkers(), the general walk) over those lists.  The fused kernel's
-// register peak is the walker pool's (119 VGPRs: 4 waves per SIMD), which
-// C2 and C3 - nearly nothing deferred - paid for in latency hiding.
+// One launch per batch, as the fused schedule.  dissect_fast first runs the
+// fast walk of every tile with two tiles' chunks in flight per wave (3
+// resident blocks per CU, NSD_FAST_BPC; the loop's registers and LDS are
+// only what the fast walk needs), writes the records of the packets it
+// finishes, sums the ICMPv4 messages they leave pending and appends every
+// packet it cannot finish to its wave's deferral list.  A block whose waves
+// deferred packets then walks them itself: each wave runs the walker pool
+// (walkers(), the general walk) over its own list (walk_lists), in the same
+// LDS words as the fast rows.  The fused kernel's tile loop carries the
+// walker pool's registers through every tile, which C2 and C3 - nearly
+// nothing deferred - paid for in latency hiding.
 //
 // A fast wave's list (`cap` slots of 32 bytes):
 //   deferrals from the front: { packet, data | tail << 16,
@@ -1708,29 +1666,10 @@ __global__ __launch_bounds__(BLOCK, NSD_MINW) void dissect_all(
 //   pending ICMPv4 checksums from the back: { packet, off | len << 16,
 //     the message's words before off, summed and weighted like the pass
 //     (below) }, { descriptor }
-// and its counts at cnts[wave] = { deferrals, checksums }.  The descriptor
-// rides along so the walker kernel and the checksum pass read no desc[]
-// (and the walker kernel knows the next chunk's window addresses early).
+// The descriptor rides along so the tail and the checksum pass read no
+// desc[] (and the tail knows the next chunk's window addresses early).
 
 constexpr int FROW = WIN1 / 4;   // fast rows: 16 dwords, 16-byte slots XOR-swizzled by swz_of(q, 4)
-#ifndef NSD_FAST_MINW
-#define NSD_FAST_MINW (NSD_FAST_DEPTH > 1 ? 4 : 6)   // waves per SIMD dissect_fast is register-allocated for (compact records)
-#endif
-#ifndef NSD_FAST_MINW_FULL
-#define NSD_FAST_MINW_FULL (NSD_FAST_DEPTH > 1 ? 4 : 5)   // the same for 16-byte records (the deferral entries carry layer starts)
-#endif
-#ifndef NSD_PLAIN_COUNT
-#define NSD_PLAIN_COUNT 1          // plain tiles count from three ballots (dissect_fast)
-#endif
-#ifndef NSD_FAST_BPC
-#define NSD_FAST_BPC (NSD_FAST_DEPTH > 1 ? 3 : 0)   // resident fast blocks per CU (0: as many as fit)
-#endif
-#ifndef NSD_SPLIT_TAIL
-#define NSD_SPLIT_TAIL 1           // the fast kernel's blocks walk their own deferrals (no walker launch)
-#endif
-#ifndef NSD_FAST_CSUM_U
-#define NSD_FAST_CSUM_U 8        // interior chunk loads in flight per lane (fast_icmp_pass; 4: C3 split +4 %)
-#endif
 
 struct FastShared {
 	alignas(16) uint32_t win[WAVES][64 * FROW];   // fast rows
@@ -1864,21 +1803,17 @@ __device__ __forceinline__ void fast_tiles(FastShared &sh, const uint8_t *__rest
 	if (base >= n)
 		return;
 	uint32_t *const rows = &sh.win[wv][0];
-	// Descriptors (a lane past the batch: 0).  With a deeper prefetch they
-	// are loaded unconditionally, from a clamped index (a load under a branch
-	// leaves hipcc unsure whether it is pending, and it then waits vmcnt(0)
-	// for the chunks, i.e. for every load in flight); a lane past the batch
-	// then keeps the last packet's descriptor: it only stages that frame's
-	// window, it walks nothing (valid is false) and counts nothing.
-	// The product build runs depth 2 (inline-asm stores, 3 blocks per CU).
+	// Descriptors are loaded unconditionally, from a clamped index (a load
+	// under a branch leaves hipcc unsure whether it is pending, and it then
+	// waits vmcnt(0) for the chunks, i.e. for every load in flight); a lane
+	// past the batch keeps the last packet's descriptor: it only stages that
+	// frame's window, it walks nothing (valid is false) and counts nothing.
 	auto dsc = [&](uint32_t b) -> uint64_t {
-		if (NSD_FAST_DEPTH == 1)
-			return b < n && b + lane < n ? desc[b + lane] : 0;
 		return desc[b < n && b + lane < n ? b + lane : n - 1];
 	};
 	// One tile at `base` whose chunks are in `ch` (descriptors d0): write them
-	// to the rows, reuse `ch` for the chunks of the tile NSD_FAST_DEPTH
-	// strides on (descriptors dpre), walk the tile.
+	// to the rows, reuse `ch` for the chunks of the tile two strides on
+	// (descriptors dpre), walk the tile.
 	auto tile = [&](Chunks<WIN1> &ch, const uint64_t d0, const uint64_t dpre) {
 		const uint32_t i = base + lane;
 		const bool valid = i < n;
@@ -1887,15 +1822,10 @@ __device__ __forceinline__ void fast_tiles(FastShared &sh, const uint8_t *__rest
 		WalkOut w;
 		walk_init(w, caplen, valid ? start_id : 0);
 		stage_write_sw(rows, ch, lane);
-		// (deeper prefetch: issued past the batch's last tile too, from the
-		// clamped descriptor - loads skipped on some paths also make hipcc
-		// wait vmcnt(0))
-		if (NSD_FAST_DEPTH == 1) {
-			if (base + stride < n)
-				stage_load<WIN1>(ch, frames, dpre, lane);
-		} else {
-			stage_load<WIN1, true>(ch, frames, dpre, lane);
-		}
+		// (issued past the batch's last tile too, from the clamped
+		// descriptor - loads skipped on some paths also make hipcc wait
+		// vmcnt(0))
+		stage_load<WIN1, true>(ch, frames, dpre, lane);
 		wave_sync_lds();
 		uint32_t fw = FW_DONE;
 		const LSrc<true, WIN1> src{ rows + lane * FROW, sh.lay3, nullptr, frames + off, caplen,
@@ -1912,7 +1842,7 @@ __device__ __forceinline__ void fast_tiles(FastShared &sh, const uint8_t *__rest
 		const bool deferred = fw != FW_DONE;
 		wave_sync_lds();
 		const bool done = valid && !deferred;
-		if (NSD_PLAIN_COUNT && plain) {
+		if (plain) {
 			// a plain tile (Ethernet / IPv4 / TCP or UDP, every packet done, no
 			// ICMPv4, no leaf, no deferral): its counts straight from three
 			// ballots - packets, bad IPv4 sums, trims - and the TCP share
@@ -1981,7 +1911,7 @@ __device__ __forceinline__ void fast_tiles(FastShared &sh, const uint8_t *__rest
 		if (done)
 			put_rec_st<CR>(rec, i, w);
 		fc.add(w, caplen, done);
-		// the deferred packets' walk state, for dissect_walk: from the start
+		// the deferred packets' walk state, for walk_lists: from the start
 		// (FW_RESTART; the SLL head is run here) or where the fast walk stopped
 		// (FW_RESUME: its layers are counted here)
 		const uint64_t dm = __ballot(deferred);
@@ -2018,59 +1948,8 @@ __device__ __forceinline__ void fast_tiles(FastShared &sh, const uint8_t *__rest
 			ndef += (uint32_t)__popcll(dm);
 		}
 	};
-#if NSD_FAST_DEPTH == 1
-	// software pipeline: tile t walked while tile t+1's chunks and tile t+2's
-	// descriptors are in flight
-	uint64_t d0 = dsc(base), d1 = dsc(base + stride);
-	Chunks<WIN1> ch;
-	stage_load<WIN1>(ch, frames, d0, lane);
-	for (; base < n; base += stride) {
-		const uint64_t d2 = dsc(base + 2 * stride);
-		tile(ch, d0, d1);
-		d0 = d1;
-		d1 = d2;
-	}
-#elif NSD_FAST_DEPTH == 3
-	// three tiles' chunks in flight while one is walked: three register sets
-	// in turn (the loop unrolled by three), descriptors four tiles ahead
-	uint64_t d0 = dsc(base), d1 = dsc(base + stride), d2 = dsc(base + 2 * stride), d3 = dsc(base + 3 * stride);
-	Chunks<WIN1> chA, chB, chC;
-	stage_load<WIN1, true>(chA, frames, d0, lane);
-	stage_load<WIN1, true>(chB, frames, d1, lane);
-	stage_load<WIN1, true>(chC, frames, d2, lane);
-	for (;;) {
-		uint64_t d4 = dsc(base + 4 * stride);
-		tile(chA, d0, d3);
-		d0 = d1;
-		d1 = d2;
-		d2 = d3;
-		d3 = d4;
-		base += stride;
-		if (base >= n)
-			break;
-		d4 = dsc(base + 4 * stride);
-		tile(chB, d0, d3);
-		d0 = d1;
-		d1 = d2;
-		d2 = d3;
-		d3 = d4;
-		base += stride;
-		if (base >= n)
-			break;
-		d4 = dsc(base + 4 * stride);
-		tile(chC, d0, d3);
-		d0 = d1;
-		d1 = d2;
-		d2 = d3;
-		d3 = d4;
-		base += stride;
-		if (base >= n)
-			break;
-	}
-#else
 	// two tiles' chunks in flight while one is walked: two register sets that
 	// swap roles (the loop unrolled by two), descriptors three tiles ahead
-	static_assert(NSD_FAST_DEPTH == 2, "prefetch depth 1, 2 or 3");
 	uint64_t d0 = dsc(base), d1 = dsc(base + stride), d2 = dsc(base + 2 * stride);
 	Chunks<WIN1> chA, chB;
 	stage_load<WIN1, true>(chA, frames, d0, lane);
@@ -2093,7 +1972,6 @@ __device__ __forceinline__ void fast_tiles(FastShared &sh, const uint8_t *__rest
 		if (base >= n)
 			break;
 	}
-#endif
 	drain_stores();   // the loop's records, list entries and side words are complete
 	fc.flush(sh.cnt, lane);
 }
@@ -2167,87 +2045,23 @@ __device__ __forceinline__ void fast_icmp_pass(FastShared &sh, const uint8_t *__
 		atomicAdd(&sh.cnt[NSD_CNT_ICMP_BAD], (unsigned long long)bad);
 }
 
+// The split schedule's tail: each wave hands the deferrals of its own fast
+// loop (`list`, `cnt` entries from the front) to its walker pool
+// (walkers()), 64 of them (a chunk) at a time; then, as the fused kernel,
+// the block walks the leaves and sums the ICMPv4 checksums its walks left
+// pending (the waves' own lists at `pend`, `region` / WAVES slots per wave).
+// Chunk entries are loaded two chunks ahead, and while chunk c's walkers
+// run, the first windows of chunk c + 1 (at each packet's cursor) are
+// touched into L2 by 4-byte LDS-DMA loads (no VGPR waits for them): its
+// sessions then stage from L2.  s_touch: the touches' LDS-DMA target (never
+// read).  Block-uniform call: the pool's set-up and passes have barriers.
 template <int MODE, bool CR>
 __device__ __forceinline__ void walk_lists(Shared &sh, uint32_t *s_touch, const uint8_t *__restrict__ frames,
 					   const uint64_t *__restrict__ desc, uint32_t n, void *__restrict__ rec,
 					   uint32_t *__restrict__ ext, uint32_t ext_words, uint32_t *__restrict__ ext_used,
 					   uint32_t chunk, unsigned long long *__restrict__ counters,
-					   const uint4 *__restrict__ lists, uint32_t cap, const uint2 *__restrict__ cnts,
-					   uint32_t nlists, uint32_t nw, uint64_t *__restrict__ pend, uint32_t region);
-
-// The split schedule's fast kernel.  `tail` (NSD_SPLIT_TAIL): a block whose
-// waves deferred packets walks them itself after its tiles (walk_lists over
-// its own four lists, the walker pool's LDS in the same words as the fast
-// rows), so a batch the fast walk finishes takes one launch instead of two
-// (C2: the walker kernel's empty launch cost 4.9 us of 205, at any grid).
-template <int MODE, bool CR>
-__global__ __launch_bounds__(BLOCK, CR ? NSD_FAST_MINW : NSD_FAST_MINW_FULL) void dissect_fast(
-	const uint8_t *__restrict__ frames, const uint64_t *__restrict__ desc, uint32_t n, int start_id,
-	void *__restrict__ rec, unsigned long long *__restrict__ counters, uint4 *__restrict__ lists, uint32_t cap,
-	uint2 *__restrict__ cnts, const uint32_t *__restrict__ sll, uint32_t *__restrict__ side,
-	unsigned long long *__restrict__ sched, uint32_t *__restrict__ ext, uint32_t ext_words,
-	uint32_t *__restrict__ ext_used, uint32_t chunk, uint64_t *__restrict__ pend, uint32_t region, uint32_t tail)
-{
-	constexpr int SW = 2;
-	union FastLds {
-		FastShared f;
-		Shared w;
-	};
-	__shared__ FastLds su;
-	FastShared &sh = su.f;
-	if (threadIdx.x < 32)
-		sh.ops[threadIdx.x] = 0;
-	block_init(sh.cnt, sh.lay3);
-	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-	const uint32_t gw = blockIdx.x * WAVES + wv;
-	uint32_t ndef = 0, nicmp = 0;
-	fast_tiles<MODE, CR>(sh, frames, desc, n, start_id, rec, sll, side, lists + (size_t)gw * cap * SW, cap, ndef,
-			     nicmp);
-	if (lane == 0) {
-		cnts[gw] = make_uint2(ndef, nicmp);
-		sh.pcnt[wv] = nicmp;
-		if (sched && ndef)
-			atomicAdd(&sched[0], (unsigned long long)ndef);
-		if (sched && nicmp)
-			atomicAdd(&sched[1], (unsigned long long)nicmp);
-	}
-	if (MODE == PRINT_NORM) {
-		__syncthreads();   // records final, the block's pending lists and counts complete
-		fast_icmp_pass<NSD_FAST_CSUM_U, CR>(sh, frames, desc, rec, lists, cap);
-	}
-	block_flush(sh.cnt, counters);
-	if (threadIdx.x < 32 && sh.ops[threadIdx.x])
-		atomicAdd(&counters[NSD_CNT_OPS + threadIdx.x], (unsigned long long)sh.ops[threadIdx.x]);
-	if constexpr (NSD_SPLIT_TAIL && (MODE == PRINT_NORM || MODE == PRINT_LESS)) {
-		// (the barrier also orders the flush's LDS reads before the walker
-		// pool's set-up in the same words)
-		if (__syncthreads_or(tail && ndef != 0)) {
-			__shared__ uint32_t s_touch[64];
-			walk_lists<MODE, CR>(su.w, s_touch, frames, desc, n, rec, ext, ext_words, ext_used, chunk, counters,
-					     lists, cap, cnts, gridDim.x * WAVES, gridDim.x * WAVES, pend, region);
-		}
-	}
-}
-
-// The walker kernel: wave g of the grid takes the fast kernel's lists g,
-// g + W, g + 2W, ... (W = this grid's waves), 64 deferrals (a chunk) at a
-// time, and hands them to its walker pool (walkers()); then, as the fused
-// kernel, the leaves and ICMPv4 checksums its walks left pending (its own
-// lists, `region` / WAVES slots per wave).  Chunk entries are loaded two
-// chunks ahead, and while chunk c's walkers run, the first windows of chunk
-// c + 1 (at each packet's cursor) are touched into L2 by 4-byte LDS-DMA loads
-// (no VGPR waits for them): its sessions then stage from L2.
-// The walker pool over the fast kernel's deferral lists: wave gw takes lists
-// gw, gw + nw, ... (nw: the list stride; the fast kernel's own tail passes
-// nlists, so each wave takes its own list only), then the block's leaves and
-// ICMPv4 checksums.  s_touch: the L2 touches' LDS-DMA target (never read).
-template <int MODE, bool CR>
-__device__ __forceinline__ void walk_lists(Shared &sh, uint32_t *s_touch, const uint8_t *__restrict__ frames,
-					   const uint64_t *__restrict__ desc, uint32_t n, void *__restrict__ rec,
-					   uint32_t *__restrict__ ext, uint32_t ext_words, uint32_t *__restrict__ ext_used,
-					   uint32_t chunk, unsigned long long *__restrict__ counters,
-					   const uint4 *__restrict__ lists, uint32_t cap, const uint2 *__restrict__ cnts,
-					   uint32_t nlists, uint32_t nw, uint64_t *__restrict__ pend, uint32_t region)
+					   const uint4 *__restrict__ list, uint32_t cnt, uint64_t *__restrict__ pend,
+					   uint32_t region)
 {
 	constexpr int SW = 2;
 	if (threadIdx.x < 64)
@@ -2274,44 +2088,29 @@ __device__ __forceinline__ void walk_lists(Shared &sh, uint32_t *s_touch, const 
 	wk.stage = false;
 	WalkOut pw;
 	walk_init(pw, 0, 0);
-	RingSt rs;   // (unused: the walker kernel stores its records at once)
+	RingSt rs;   // (unused: the tail stores its records at once)
 	rs.init();
 
-	// chunk positions (wave-uniform): list L, first entry k0, the list's count
-	struct Pos {
-		uint32_t L, k0, cnt;
-	};
-	auto adv = [&](Pos p) -> Pos {
-		p.k0 += 64;
-		while (p.L < nlists && p.k0 >= p.cnt) {
-			p.L += nw;
-			p.k0 = 0;
-			p.cnt = p.L < nlists ? min(cnts[p.L].x, cap) : 0u;
-		}
-		return p;
-	};
-	auto load = [&](const Pos &p, uint4 &x0, uint4 &x1) {
+	// the chunk at entry k0 (wave-uniform): lanes past the list's count load nothing
+	auto load = [&](uint32_t k0, uint4 &x0, uint4 &x1) {
 		x0 = x1 = make_uint4(0, 0, 0, 0);
-		if (p.L < nlists && p.k0 + lane < p.cnt) {
-			const uint4 *e = lists + ((size_t)p.L * cap + p.k0 + lane) * SW;
+		if (k0 + lane < cnt) {
+			const uint4 *e = list + (size_t)(k0 + lane) * SW;
 			x0 = e[0];
 			x1 = e[1];
 		}
 	};
-	Pos p0 = adv(Pos{ gw, 0u - 64u, gw < nlists ? min(cnts[gw].x, cap) : 0u });
-	Pos p1 = adv(p0);
 	uint4 c0, c1, n0, n1;
-	load(p0, c0, c1);
-	load(p1, n0, n1);
-	while (p0.L < nlists) {
-		const Pos p2 = adv(p1);
+	load(0, c0, c1);
+	load(64, n0, n1);
+	for (uint32_t k0 = 0; k0 < cnt; k0 += 64) {
 		{
 			// the next chunk's first windows into L2: [cursor, +WIN2) in aligned
 			// coordinates, one or two 128-byte lines
 			const uint64_t d = (uint64_t)n1.y << 32 | n1.x;
 			const uint32_t m = (uint32_t)NSD_DESC_OFF(d) & 15, caplen = NSD_DESC_CAPLEN(d);
 			const uint32_t wb = ((n0.y & 0xFFFF) + m) & ~15u;
-			const bool on = p1.L < nlists && p1.k0 + lane < p1.cnt && wb < caplen + m;
+			const bool on = k0 + 64 + lane < cnt && wb < caplen + m;
 			const uint64_t a = (uint64_t)frames + (NSD_DESC_OFF(d) & ~15ull) + wb;
 			const bool two = on && (a & 127) != 0 && wb + (128 - (uint32_t)(a & 127)) < caplen + m;
 			if (on)
@@ -2322,8 +2121,8 @@ __device__ __forceinline__ void walk_lists(Shared &sh, uint32_t *s_touch, const 
 								 (__attribute__((address_space(3))) void *)s_touch, 4, 0, 0);
 		}
 		uint4 m0, m1;
-		load(p2, m0, m1);
-		bool pnd = p0.k0 + lane < p0.cnt;
+		load(k0 + 128, m0, m1);
+		bool pnd = k0 + lane < cnt;
 		const uint32_t pi = c0.x;
 		const uint64_t pd = (uint64_t)c1.y << 32 | c1.x;
 		walk_init(pw, c0.y >> 16, (int)(c0.z >> 27));
@@ -2343,8 +2142,6 @@ __device__ __forceinline__ void walk_lists(Shared &sh, uint32_t *s_touch, const 
 		c1 = n1;
 		n0 = m0;
 		n1 = m1;
-		p0 = p1;
-		p1 = p2;
 	}
 	{
 		bool none = false;
@@ -2364,29 +2161,57 @@ __device__ __forceinline__ void walk_lists(Shared &sh, uint32_t *s_touch, const 
 		atomicAdd(&counters[NSD_CNT_OPS + threadIdx.x], (unsigned long long)sh.ops[threadIdx.x]);
 }
 
+// The split schedule's kernel.  A block whose waves deferred packets walks
+// them itself after its tiles (walk_lists, each wave over its own list, the
+// walker pool's LDS in the same words as the fast rows), so a batch the
+// fast walk finishes costs no second launch (C2: a walker kernel's empty
+// launch cost 4.9 us of 205, at any grid).
 template <int MODE, bool CR>
-__global__ __launch_bounds__(BLOCK, NSD_MINW) void dissect_walk(
-	const uint8_t *__restrict__ frames, const uint64_t *__restrict__ desc, uint32_t n,
-	void *__restrict__ rec, uint32_t *__restrict__ ext, uint32_t ext_words,
-	uint32_t *__restrict__ ext_used, uint32_t chunk, unsigned long long *__restrict__ counters,
-	const uint4 *__restrict__ lists, uint32_t cap, const uint2 *__restrict__ cnts, uint32_t nlists,
+__global__ __launch_bounds__(BLOCK, CR ? NSD_FAST_MINW : NSD_FAST_MINW_FULL) void dissect_fast(
+	const uint8_t *__restrict__ frames, const uint64_t *__restrict__ desc, uint32_t n, int start_id,
+	void *__restrict__ rec, unsigned long long *__restrict__ counters, uint4 *__restrict__ lists, uint32_t cap,
+	const uint32_t *__restrict__ sll, uint32_t *__restrict__ side, unsigned long long *__restrict__ sched,
+	uint32_t *__restrict__ ext, uint32_t ext_words, uint32_t *__restrict__ ext_used, uint32_t chunk,
 	uint64_t *__restrict__ pend, uint32_t region)
 {
-	__shared__ Shared sh;
-	__shared__ uint32_t s_touch[64];
-	{
-		// nothing deferred to this block's waves (the common case of traffic
-		// the fast walk finishes): leave before any set-up
-		const uint32_t nw = gridDim.x * WAVES;
-		bool any = false;
-		for (uint32_t L = blockIdx.x * WAVES + (threadIdx.x % WAVES) + (threadIdx.x / WAVES) * nw; L < nlists;
-		     L += (BLOCK / WAVES) * nw)
-			any = any || cnts[L].x != 0;
-		if (!__syncthreads_or(any))
-			return;
+	constexpr int SW = 2;
+	union FastLds {
+		FastShared f;
+		Shared w;
+	};
+	__shared__ FastLds su;
+	FastShared &sh = su.f;
+	if (threadIdx.x < 32)
+		sh.ops[threadIdx.x] = 0;
+	block_init(sh.cnt, sh.lay3);
+	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+	const uint32_t gw = blockIdx.x * WAVES + wv;
+	uint4 *const list = lists + (size_t)gw * cap * SW;   // this wave's
+	uint32_t ndef = 0, nicmp = 0;
+	fast_tiles<MODE, CR>(sh, frames, desc, n, start_id, rec, sll, side, list, cap, ndef, nicmp);
+	if (lane == 0) {
+		sh.pcnt[wv] = nicmp;
+		if (sched && ndef)
+			atomicAdd(&sched[0], (unsigned long long)ndef);
+		if (sched && nicmp)
+			atomicAdd(&sched[1], (unsigned long long)nicmp);
 	}
-	walk_lists<MODE, CR>(sh, s_touch, frames, desc, n, rec, ext, ext_words, ext_used, chunk, counters, lists, cap,
-			     cnts, nlists, gridDim.x * WAVES, pend, region);
+	if (MODE == PRINT_NORM) {
+		__syncthreads();   // records final, the block's pending lists and counts complete
+		fast_icmp_pass<NSD_FAST_CSUM_U, CR>(sh, frames, desc, rec, lists, cap);
+	}
+	block_flush(sh.cnt, counters);
+	if (threadIdx.x < 32 && sh.ops[threadIdx.x])
+		atomicAdd(&counters[NSD_CNT_OPS + threadIdx.x], (unsigned long long)sh.ops[threadIdx.x]);
+	if constexpr (MODE == PRINT_NORM || MODE == PRINT_LESS) {
+		// (the barrier also orders the flush's LDS reads before the walker
+		// pool's set-up in the same words)
+		if (__syncthreads_or(ndef != 0)) {
+			__shared__ uint32_t s_touch[64];
+			walk_lists<MODE, CR>(su.w, s_touch, frames, desc, n, rec, ext, ext_words, ext_used, chunk, counters,
+					     list, min(ndef, cap), pend, region);
+		}
+	}
 }
 
 } // namespace nsd
@@ -2413,7 +2238,7 @@ static uint32_t region_for(uint32_t n, uint32_t blocks)
 // NSD_CNT_LISTOVF.)
 static uint32_t region_for_fused(uint32_t n, uint32_t blocks, bool compact)
 {
-	return NSD_GROUP_TILES && compact ? 2 * region_for(n, blocks) + nsd::WAVES * 4 * 64 : region_for(n, blocks);
+	return compact ? 2 * region_for(n, blocks) + nsd::WAVES * 4 * 64 : region_for(n, blocks);
 }
 
 // worst case over grids: sum of regions <= n + blocks * BLOCK
@@ -2423,14 +2248,15 @@ static size_t region_slots(uint32_t n)
 }
 
 // ---- the schedule -------------------------------------------------------------
-// split (dissect_fast + dissect_walk) or fused (dissect_all).  The split
-// schedule runs the fast walk at 6 waves per SIMD instead of 4 and wins when
-// the fast walk finishes nearly every packet and few ICMPv4 messages run
-// past their windows (C2 16M x 64 B: 0.233 against 0.249 ms).  When many
-// packets need the general walk (C4's IPv6 extension chains) the fused
-// kernel wins by far (1.17 against 1.88 ms): its walkers take a tile's
-// packets while their first lines are still on chip, where the walker
-// kernel re-reads them and the fast kernel writes a list entry per packet.
+// split (dissect_fast) or fused (dissect_all), one launch either way.  The
+// split schedule runs a fast loop with two tiles in flight per wave and
+// none of the walker pool's state, and wins when the fast walk finishes
+// nearly every packet and few ICMPv4 messages run past their windows (C2
+// 16M x 64 B: 0.233 against 0.249 ms).  When many packets need the general
+// walk (C4's IPv6 extension chains) the fused kernel wins by far (1.17
+// against 1.88 ms): its walkers take a tile's packets while their first
+// lines are still on chip, where the split schedule's tail re-reads them
+// and its fast loop writes a list entry per packet.
 // When many ICMPv4 checksums are left to a pass (C3 IMIX: about a fifth of
 // the packets) the fused kernel wins too (0.70 - 0.75 against 0.73 - 0.81
 // ms on the same boxes, r03): its checksum pass streams at 4 waves per SIMD
@@ -2456,17 +2282,8 @@ static size_t region_slots(uint32_t n)
 // +0.7 %, in the same kernel) and with the record ring (RingSt: C4's writes
 // halved, C3 +3 % with it; on until the first sample is read).  State is per
 // device.
-#ifndef NSD_SCHED_SAMPLE
-#define NSD_SCHED_SAMPLE 32
-#endif
 namespace {
 constexpr int MAX_DEV = 16;
-#ifndef NSD_SMALL_FRAME
-#define NSD_SMALL_FRAME 128
-#endif
-#ifndef NSD_FAST_BPC_SMALL
-#define NSD_FAST_BPC_SMALL 2
-#endif
 struct Sched {
 	bool init = false, fused = false, pending = false, small = false;
 	bool walky = false;                    // the sample's deferred share above 25 % (no progress priority)
@@ -2519,10 +2336,13 @@ Plan sched_plan(uint32_t n, unsigned long long *pair, const uint64_t *counters, 
 	const bool capturing = hipStreamIsCapturing(stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
 	// (a sample is read only once sched_sampled has recorded its event: between
 	// the plan and that record, the event still stands for an older sample, and
-	// another stream's launch must not take the copies in flight for it)
-	if (!capturing && S.pending && S.recorded && hipEventQuery(S.ev) == hipSuccess && S.discard) {
+	// another stream's launch must not take the copies in flight for it).
+	// One query: an event that completed between two would let a failed
+	// sample's half-landed words pass for a sample.
+	const bool landed = !capturing && S.pending && S.recorded && hipEventQuery(S.ev) == hipSuccess;
+	if (landed && S.discard) {
 		S.pending = S.recorded = S.discard = false;
-	} else if (!capturing && S.pending && S.recorded && hipEventQuery(S.ev) == hipSuccess) {
+	} else if (landed) {
 		const double rd = S.sampled ? (double)S.host[0] / (double)S.sampled : 0.0;
 		const double ri = S.sampled ? (double)S.host[1] / (double)S.sampled : 0.0;
 		S.fused = S.fused ? rd > 0.05 || ri > 0.05 : rd > 0.15 || ri > 0.10;
@@ -2633,8 +2453,9 @@ extern "C" int nsd_last_schedule(void)
 }
 
 // workspace: the fused kernel's pending lists (u64 per slot); the split
-// schedule's fast lists (up to 32 bytes per slot), their counts and the
-// walker kernel's pending lists (u64 per slot, up to two per packet slot)
+// schedule's fast lists (up to 32 bytes per slot), a region no kernel uses
+// (8 bytes per fast wave: the size callers allocate is kept) and its tail's
+// pending lists (u64 per slot, of the 16 bytes per packet slot kept there)
 static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 // (the last 256 bytes: the schedule sample's pair, at sched_pair_at)
 // (then the fused kernel's group tile counters: a 128-byte line per block
@@ -2722,119 +2543,85 @@ extern "C" int nsd_launch_dissect_rec(const uint8_t *d_frames, const uint64_t *d
 	const Plan plan = sched_plan(n, mi != 2 ? pair : nullptr, d_counters, stream);
 	const int s_cus = plan.cus;
 	unsigned long long *const sched = plan.sample ? pair : nullptr;
-	const bool fused = mi != 2 && plan.fused;
-	if (fused) {
-	typedef void (*kfn)(const uint8_t *, const uint64_t *, uint32_t, int, void *, uint32_t *, uint32_t,
-			    uint32_t *, uint32_t, unsigned long long *, uint64_t *, uint32_t, const uint32_t *,
-			    unsigned long long *, uint32_t *, uint32_t);
-	static const kfn kernels[2][3] = {
-		{ dissect_all<PRINT_NORM, false>, dissect_all<PRINT_LESS, false>, dissect_all<PRINT_HEX, false> },
-		{ dissect_all<PRINT_NORM, true>, dissect_all<PRINT_LESS, true>, dissect_all<PRINT_HEX, true> },
+	// after a kernel launch: a launch error drops the sample and fails the call
+	auto launched = [&]() {
+		if (hipGetLastError() == hipSuccess)
+			return true;
+		if (sched)
+			sched_abort(stream);
+		return false;
 	};
-	// compact records of walker-heavy batches: the record ring's build (an
-	// instantiation of its own: beside the ring's code, the records held one
-	// tile in registers spill, and without them C3 runs 4 % slower)
-	static const kfn ring_kernels[2] = { dissect_all<PRINT_NORM, true, true>, dissect_all<PRINT_LESS, true, true> };
-	static std::atomic<int> s_occ[2][3], s_rocc[2];
-	const bool ring = NSD_RING && plan.ring && ci == 1 && mi < 2;
-	const kfn f = ring ? ring_kernels[mi] : kernels[ci][mi];
-	std::atomic<int> &occ_slot = ring ? s_rocc[mi] : s_occ[ci][mi];
-	uint32_t cap_blocks = grid > 0 ? (uint32_t)grid : (uint32_t)(s_cus * occupancy((const void *)f, occ_slot, 4));
-	if (cap_blocks > NSD_MAX_GRID)
-		cap_blocks = NSD_MAX_GRID;
-	const uint32_t blocks = want < cap_blocks ? want : cap_blocks;
-	// the CU groups' tile counters (walk_tiles), a 128-byte line each, zeroed
-	// on the launch's stream
-	uint32_t *const gtiles = (uint32_t *)((uint8_t *)d_ws + gtiles_at(n));
-	if (NSD_GROUP_TILES && compact) {
-		hipLaunchKernelGGL(zero_tiles, dim3((blocks + 255) / 256), dim3(256), 0, stream, gtiles, blocks);
-		if (hipGetLastError() != hipSuccess) {
-			if (sched)
-				sched_abort(stream);
-			return -2;
+	if (mi != 2 && plan.fused) {
+		typedef void (*kfn)(const uint8_t *, const uint64_t *, uint32_t, int, void *, uint32_t *, uint32_t,
+				    uint32_t *, uint32_t, unsigned long long *, uint64_t *, uint32_t, const uint32_t *,
+				    unsigned long long *, uint32_t *, uint32_t);
+		static const kfn kernels[2][3] = {
+			{ dissect_all<PRINT_NORM, false>, dissect_all<PRINT_LESS, false>, dissect_all<PRINT_HEX, false> },
+			{ dissect_all<PRINT_NORM, true>, dissect_all<PRINT_LESS, true>, dissect_all<PRINT_HEX, true> },
+		};
+		// compact records of walker-heavy batches: the record ring's build (an
+		// instantiation of its own: beside the ring's code, the records held one
+		// tile in registers spill, and without them C3 runs 4 % slower)
+		static const kfn ring_kernels[2] = { dissect_all<PRINT_NORM, true, true>,
+						     dissect_all<PRINT_LESS, true, true> };
+		static std::atomic<int> s_occ[2][3], s_rocc[2];
+		const bool ring = plan.ring && ci == 1 && mi < 2;
+		const kfn f = ring ? ring_kernels[mi] : kernels[ci][mi];
+		std::atomic<int> &occ_slot = ring ? s_rocc[mi] : s_occ[ci][mi];
+		uint32_t cap_blocks = grid > 0 ? (uint32_t)grid
+					       : (uint32_t)(s_cus * occupancy((const void *)f, occ_slot, 4));
+		if (cap_blocks > NSD_MAX_GRID)
+			cap_blocks = NSD_MAX_GRID;
+		const uint32_t blocks = want < cap_blocks ? want : cap_blocks;
+		// the CU groups' tile counters (walk_tiles), a 128-byte line each, zeroed
+		// on the launch's stream
+		uint32_t *const gtiles = (uint32_t *)((uint8_t *)d_ws + gtiles_at(n));
+		if (compact) {
+			hipLaunchKernelGGL(zero_tiles, dim3((blocks + 255) / 256), dim3(256), 0, stream, gtiles, blocks);
+			if (!launched())
+				return -2;
 		}
+		hipLaunchKernelGGL(f, dim3(blocks), dim3(BLOCK), 0, stream, d_frames, d_desc, n, start_id, d_rec, d_ext,
+				   ext_words, d_ext_used, chunk_for(blocks), (unsigned long long *)d_counters,
+				   (uint64_t *)d_ws, region_for_fused(n, blocks, compact), (const uint32_t *)d_sll, sched,
+				   gtiles, plan.prio ? 1u : 0u);
+	} else {
+		typedef void (*ffn)(const uint8_t *, const uint64_t *, uint32_t, int, void *, unsigned long long *, uint4 *,
+				    uint32_t, const uint32_t *, uint32_t *, unsigned long long *, uint32_t *, uint32_t,
+				    uint32_t *, uint32_t, uint64_t *, uint32_t);
+		static const ffn fast[2][3] = {
+			{ dissect_fast<PRINT_NORM, false>, dissect_fast<PRINT_LESS, false>, dissect_fast<PRINT_HEX, false> },
+			{ dissect_fast<PRINT_NORM, true>, dissect_fast<PRINT_LESS, true>, dissect_fast<PRINT_HEX, true> },
+		};
+		static std::atomic<int> s_focc[2][3];
+		// grid > 0 (tests): the grid capped at `grid` blocks
+		uint32_t fcap = grid > 0 ? (uint32_t)grid
+					 : (uint32_t)(s_cus * occupancy((const void *)fast[ci][mi], s_focc[ci][mi], 8));
+		// with two tiles in flight per wave, 3 blocks per CU outrun the 4 that
+		// fit (HBM serves fewer concurrent streams better), and 2
+		// the 3 when the frames are small (the sample, sched_plan)
+		const int bpc = plan.small ? NSD_FAST_BPC_SMALL : NSD_FAST_BPC;
+		if (grid <= 0 && bpc > 0 && fcap > (uint32_t)(s_cus * bpc))
+			fcap = (uint32_t)(s_cus * bpc);
+		if (fcap > NSD_MAX_GRID)
+			fcap = NSD_MAX_GRID;
+		const uint32_t fblocks = want < fcap ? want : fcap;
+		const uint32_t cap = region_for(n, fblocks) / WAVES;   // slots per fast wave
+		const uint32_t nlists = fblocks * WAVES;
+		const size_t slotb = 32;   // a list slot: two uint4 (fast_tiles)
+		uint8_t *ws = (uint8_t *)d_ws;
+		uint4 *lists = (uint4 *)ws;
+		// the tail's pending lists, `cap` u64 slots per wave (a packet the tail
+		// walks adds at most one entry), past 8 unused bytes per list
+		uint64_t *pend = (uint64_t *)(ws + align256(slotb * nlists * cap) + align256((size_t)nlists * 8));
+		// compact records: the pool's side words (when it has them), for leaf ends
+		uint32_t *side = compact && d_ext && ext_words >= n ? d_ext : nullptr;
+		hipLaunchKernelGGL(fast[ci][mi], dim3(fblocks), dim3(BLOCK), 0, stream, d_frames, d_desc, n, start_id,
+				   d_rec, (unsigned long long *)d_counters, lists, cap, (const uint32_t *)d_sll, side, sched,
+				   d_ext, ext_words, d_ext_used, chunk_for(fblocks), pend, cap * WAVES);
 	}
-	hipLaunchKernelGGL(f, dim3(blocks), dim3(BLOCK), 0, stream, d_frames, d_desc, n, start_id, d_rec, d_ext,
-			   ext_words, d_ext_used, chunk_for(blocks), (unsigned long long *)d_counters, (uint64_t *)d_ws,
-			   region_for_fused(n, blocks, compact), (const uint32_t *)d_sll, sched, gtiles,
-			   plan.prio ? 1u : 0u);
-	if (hipGetLastError() != hipSuccess) {
-		if (sched)
-			sched_abort(stream);
+	if (!launched())
 		return -2;
-	}
-	if (sched)
-		sched_sampled(sched, d_counters, stream);
-	return 0;
-	}
-	typedef void (*ffn)(const uint8_t *, const uint64_t *, uint32_t, int, void *, unsigned long long *, uint4 *,
-			    uint32_t, uint2 *, const uint32_t *, uint32_t *, unsigned long long *, uint32_t *, uint32_t,
-			    uint32_t *, uint32_t, uint64_t *, uint32_t, uint32_t);
-	typedef void (*wfn)(const uint8_t *, const uint64_t *, uint32_t, void *, uint32_t *, uint32_t, uint32_t *,
-			    uint32_t, unsigned long long *, const uint4 *, uint32_t, const uint2 *, uint32_t, uint64_t *,
-			    uint32_t);
-	static const ffn fast[2][3] = {
-		{ dissect_fast<PRINT_NORM, false>, dissect_fast<PRINT_LESS, false>, dissect_fast<PRINT_HEX, false> },
-		{ dissect_fast<PRINT_NORM, true>, dissect_fast<PRINT_LESS, true>, dissect_fast<PRINT_HEX, true> },
-	};
-	static const wfn walk[2][2] = {
-		{ dissect_walk<PRINT_NORM, false>, dissect_walk<PRINT_LESS, false> },
-		{ dissect_walk<PRINT_NORM, true>, dissect_walk<PRINT_LESS, true> },
-	};
-	static std::atomic<int> s_focc[2][3], s_wocc[2][2];
-	// grid > 0 (tests): both kernels' grids capped at `grid` blocks
-	uint32_t fcap = grid > 0 ? (uint32_t)grid
-				 : (uint32_t)(s_cus * occupancy((const void *)fast[ci][mi], s_focc[ci][mi], 8));
-	// with two tiles in flight per wave, 3 blocks per CU outrun the 4 that
-	// fit (HBM serves fewer concurrent streams better), and 2
-	// the 3 when the frames are small (the sample, sched_plan)
-	const int bpc = plan.small ? NSD_FAST_BPC_SMALL : NSD_FAST_BPC;
-	if (grid <= 0 && bpc > 0 && fcap > (uint32_t)(s_cus * bpc))
-		fcap = (uint32_t)(s_cus * bpc);
-	if (fcap > NSD_MAX_GRID)
-		fcap = NSD_MAX_GRID;
-	const uint32_t fblocks = want < fcap ? want : fcap;
-	const uint32_t cap = region_for(n, fblocks) / WAVES;   // slots per fast wave
-	const uint32_t nlists = fblocks * WAVES;
-	const size_t slotb = 32;   // a list slot: two uint4 (fast_tiles)
-	uint8_t *ws = (uint8_t *)d_ws;
-	uint4 *lists = (uint4 *)ws;
-	uint2 *cnts = (uint2 *)(ws + align256(slotb * nlists * cap));
-	uint64_t *pend = (uint64_t *)((uint8_t *)cnts + align256((size_t)nlists * 8));
-	// compact records: the pool's side words (when it has them), for leaf ends
-	uint32_t *side = compact && d_ext && ext_words >= n ? d_ext : nullptr;
-	// NSD_SPLIT_TAIL: each fast block walks its own deferrals, one list per
-	// wave (`region` = cap slots of walker pending entries per wave)
-	const bool tail = NSD_SPLIT_TAIL && mi != 2;
-	hipLaunchKernelGGL(fast[ci][mi], dim3(fblocks), dim3(BLOCK), 0, stream, d_frames, d_desc, n, start_id, d_rec,
-			   (unsigned long long *)d_counters, lists, cap, cnts, (const uint32_t *)d_sll, side, sched, d_ext,
-			   ext_words, d_ext_used, chunk_for(fblocks), pend, cap * WAVES, tail ? 1u : 0u);
-	if (hipGetLastError() != hipSuccess) {
-		if (sched)
-			sched_abort(stream);
-		return -2;
-	}
-	if (mi == 2 || tail) {
-		if (sched && tail)
-			sched_sampled(sched, d_counters, stream);
-		return 0;   // no chains: nothing deferred; or the fast blocks walked their own
-	}
-	uint32_t wcap = grid > 0 ? (uint32_t)grid
-				 : (uint32_t)(s_cus * occupancy((const void *)walk[ci][mi], s_wocc[ci][mi], 4));
-#ifdef NSD_WALK_GRID_CAP
-	if (wcap > NSD_WALK_GRID_CAP)
-		wcap = NSD_WALK_GRID_CAP;
-#endif
-	const uint32_t wblocks = fblocks < wcap ? fblocks : wcap;
-	const uint32_t per_wave = (nlists + wblocks * WAVES - 1) / (wblocks * WAVES);   // lists per walker wave
-	hipLaunchKernelGGL(walk[ci][mi], dim3(wblocks), dim3(BLOCK), 0, stream, d_frames, d_desc, n, d_rec, d_ext,
-			   ext_words, d_ext_used, chunk_for(wblocks), (unsigned long long *)d_counters, lists, cap, cnts,
-			   nlists, pend, per_wave * cap * WAVES);
-	if (hipGetLastError() != hipSuccess) {
-		if (sched)
-			sched_abort(stream);
-		return -2;
-	}
 	if (sched)
 		sched_sampled(sched, d_counters, stream);
 	return 0;

@@ -397,6 +397,69 @@ def test_walker_pool_mixed_tiles(grid, mode):
         _check_compact(frames, desc, mode)
 
 
+_TAIL_BATCH = []
+
+
+def _split_tail_batch():
+    """(frames, desc, chain mask), built once and never written: 1,041 long
+    chains (every one deferred: its transport header starts at byte 70 or
+    later) and 200 packets of _mixed_tiles() (leaves, ICMPv4 past the window,
+    plain packets) in 20 tiles.  Tiles 3, 7, 11, 15 hold chains only; the
+    other full tiles hold 52 chains and 12 mixed packets (lanes 2, 7, .. 57);
+    the last tile holds 5 chains and 20 mixed packets.  With a 1-block grid
+    (tile t on wave t % 4) the waves' deferral lists hold at least 260, 260,
+    260 and 261 entries: four full 64-entry chunks and a partial fifth."""
+    if not _TAIL_BATCH:
+        chains = _long_chains(64 * 4 * 4 + 17)
+        mixed = _mixed_tiles()[::27][:200]
+        n = len(chains) + len(mixed)
+        assert (len(chains), len(mixed), n) == (1041, 200, 19 * 64 + 25)
+        pkts, is_chain = [], np.zeros(n, dtype=bool)
+        ci = mi = 0
+        for p in range(n):
+            tile, lane = divmod(p, 64)
+            if tile < 19:
+                is_chain[p] = tile % 4 == 3 or lane % 5 != 2 or lane >= 60
+            else:
+                is_chain[p] = lane < 5
+            if is_chain[p]:
+                pkts.append(chains[ci])
+                ci += 1
+            else:
+                pkts.append(mixed[mi])
+                mi += 1
+        assert ci == len(chains) and mi == len(mixed)
+        frames, desc = T.batch_from_packets(pkts, align=2)
+        _TAIL_BATCH.append((frames, desc, is_chain))
+    return _TAIL_BATCH[0]
+
+
+@pytest.mark.parametrize("grid", [1, 3])
+@pytest.mark.parametrize("mode", [T.PRINT_NORM, T.PRINT_LESS])
+def test_split_tail_long_lists(mode, grid):
+    """The split schedule's tail (walk_lists) over deferral lists of more than
+    one 64-entry chunk: the chunk advance, the entry loads two chunks ahead
+    and the partial last chunk.  Grid 1: every wave's list holds four full
+    chunks and a partial one; grid 3 (tile t on wave t % 12): one or two
+    chunks.  Both record forms equal the oracle's: records, ext entries, side
+    words, counters."""
+    frames, desc, is_chain = _split_tail_batch()
+    orec, _, _, _ = T.oracle_records(frames, desc, mode=mode)
+    # every chain is deferred: its last layer lies past the 64-byte fast window
+    assert (orec["data_off"][is_chain] > 64).all()
+    per_wave = np.bincount((np.arange(len(desc)) // 64) % 4, weights=is_chain, minlength=4)
+    assert (per_wave >= 256).all() and (per_wave % 64 != 0).all()
+    sched = nsd.set_schedule(nsd.SCHED_SPLIT)
+    cap = nsd.set_grid_cap(grid)
+    try:
+        _check(frames, desc, mode)
+        assert nsd.last_schedule() == "split"
+        _check_compact(frames, desc, mode)
+    finally:
+        nsd.set_schedule(sched)
+        nsd.set_grid_cap(cap)
+
+
 def _plain_tiles(seed=9, n=64 * 48):
     """Ethernet / IPv4 (no options) / TCP or UDP frames only, so whole tiles
     take the split fast kernel's plain path (plain_walk): frame lengths 42..

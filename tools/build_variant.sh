@@ -1,11 +1,12 @@
 #!/bin/bash
 # Build an experiment variant of libnsdissect.so into variants/<name>/
-# (git-ignored; travels to the GPU box with gpurun).  Tuning knobs come in as
-# -D flags; experiments that change code (e.g. skip a phase to time the
+# (git-ignored).  The numeric tunables at the top of nsd_kernels.hip come in
+# as -D flags; experiments that change code (e.g. skip a phase to time the
 # rest) are patches (paths csrc/...) applied to a scratch copy of the
-# sources, never switches in the product sources.
+# sources, never switches in the product sources.  tools/variants/ keeps
+# icmp_queue.patch, nofasticmp.patch and noicmp.patch.
 #   tools/build_variant.sh u8 -DNSD_CSUM_U=8
-#   PATCH=/tmp/nop2.patch tools/build_variant.sh nop2
+#   PATCH=tools/variants/noicmp.patch tools/build_variant.sh noicmp
 #   REV=HEAD~1 tools/build_variant.sh prev        (a committed revision's kernels)
 set -e
 cd "$(dirname "$0")/.."

@@ -91,11 +91,6 @@ def main():
                       f"{blk.mean(1).max() - blk.mean(1).min():.1f}; wave-in-block means "
                       f"{[round(float(x), 1) for x in blk.mean(0)]}", flush=True)
                 np.save(os.path.join(ROOT, "gpurun_out", "var", f"dbg_{key}.npy"), buf)
-            if os.environ.get("KB_PHASES"):
-                # counters 48..55 of an instrumented variant (tools/variants/phases.patch),
-                # summed over waves, last launch: fast-walk part, walker engine, window
-                # staging, layer steps, emit (cycles), sessions, step iterations, take (cycles)
-                print(f"{key:6s} phases {[int(x) for x in cnt[48:56]]}", flush=True)
             b.free()
             torch.cuda.empty_cache()
 
