@@ -407,7 +407,8 @@ int nsd_walk_packet_cpu(const uint8_t *pkt, uint32_t caplen, int linktype, int m
  *    NSD_N_EXT, nlayers = the count, and the batch's ext pool word i (the
  *    packet's side word) holds ids 6.. (5 bits each).  Words [0, n) of the
  *    pool are the side words when ext_words >= n (otherwise such records get
- *    NSD_F_OVERFLOW); pool entries start at word n + *d_ext_used;
+ *    NSD_F_OVERFLOW); pool entries start at word n + *d_ext_used, so a
+ *    pool of fewer than n words holds no entry either;
  *  - longer chains: chain = the ext pool slot (0xFFFFFFFF with
  *    NSD_F_OVERFLOW: pool full), nflags & 7 = NSD_N_EXT, nlayers = 0; the
  *    entry keeps the ids (offset bits 0: no cursors in this form either).
@@ -469,6 +470,18 @@ int nsd_set_grid_cap(int blocks);
  * than a quarter of the packets, and until the first sample), 1 on, 2 off.
  * Process-wide (tests); returns the previous setting, or NSD_ERR_ARG. */
 int nsd_set_record_ring(int mode);
+/* nsd_set_debug_fill (tests): with a byte 0..255 set, every batch walk
+ * first fills what it is about to write - the n records, the ext pool's
+ * ext_words words and the workspace's nsd_workspace_bytes(n) bytes - with
+ * that byte, on the launch's stream ahead of everything else it queues, so a
+ * store that never happens leaves the fill behind instead of whatever an
+ * earlier launch wrote there.  *d_ext_used and the counters accumulate and
+ * are not touched.  A launch captured into a graph is not filled (the caller
+ * fills before a replay).  -1: off (the default; the launch path then costs
+ * one relaxed atomic load more).  Process-wide, atomic; returns the previous
+ * value, -1 .. 255.  Any other argument changes nothing and returns
+ * NSD_ERR_ARG (the same number as "off": only the argument tells which). */
+int nsd_set_debug_fill(int byte);
 
 /* Compact-record pipe: nsd_pipe_create_compact as nsd_pipe_create, its
  * batches walked into nsd_crec records.  The pool needs ext_words >=

@@ -1257,11 +1257,12 @@ __device__ __forceinline__ void walk_tiles(Shared &sh, const uint8_t *__restrict
 
 	const uint32_t stride = gridDim.x * BLOCK;
 	uint64_t *const wq = pq.wq;
-	// compact records: pool words [0, n) are the packets' side words (when the
-	// pool has them), entries come after
+	// compact records: pool words [0, n) are the packets' side words, entries
+	// come after (a pool of fewer than n words has neither: an entry never
+	// lies where a consumer looks for a side word)
 	const bool side = CR && ext_words >= n;
 	const GenSink<CR> g{ ext, ext_words, ext_used, chunk, &sh.wc[wv][0], sh.ops, &sh.lay[wv][0],
-			 side ? n : 0u, side ? ext : nullptr };
+			 CR ? n : 0u, side ? ext : nullptr };
 	FlagCnt fc;
 	uint32_t ndefer = 0;
 	uint32_t base = blockIdx.x * BLOCK + wv * 64;   // this wave's tile; whole waves iterate
@@ -2076,7 +2077,7 @@ __device__ __forceinline__ void walk_lists(Shared &sh, uint32_t *s_touch, const 
 	Pending pq{ pend + (size_t)gw * (region / WAVES), region / WAVES, 0, 0 };
 	const bool side = CR && ext_words >= n;
 	const GenSink<CR> g{ ext, ext_words, ext_used, chunk, &sh.wc[wv][0], sh.ops, &sh.lay[wv][0],
-			     side ? n : 0u, side ? ext : nullptr };
+			     CR ? n : 0u, side ? ext : nullptr };   // (entries past the side words: walk_tiles)
 	FlagCnt fc;
 	Walker wk;
 	walk_init(wk.w, 0, 0);
@@ -2301,6 +2302,7 @@ std::mutex g_sched_mu;
 int g_sched_force = 0;   // 0 adaptive, NSD_SCHED_SPLIT, NSD_SCHED_FUSED
 int g_ring_force = 0;    // nsd_set_record_ring: 0 adaptive, 1 on, 2 off
 std::atomic<int> g_grid_cap{ 0 };   // nsd_set_grid_cap
+std::atomic<int> g_debug_fill{ -1 };   // nsd_set_debug_fill: -1 off, else the byte
 
 int cur_dev()
 {
@@ -2446,6 +2448,13 @@ extern "C" int nsd_set_grid_cap(int blocks)
 	return g_grid_cap.exchange(blocks);
 }
 
+extern "C" int nsd_set_debug_fill(int byte)
+{
+	if (byte < -1 || byte > 255)
+		return NSD_ERR_ARG;
+	return g_debug_fill.exchange(byte);
+}
+
 extern "C" int nsd_last_schedule(void)
 {
 	std::lock_guard<std::mutex> g(g_sched_mu);
@@ -2539,6 +2548,23 @@ extern "C" int nsd_launch_dissect_rec(const uint8_t *d_frames, const uint64_t *d
 	};
 	if (grid <= 0)
 		grid = g_grid_cap.load(std::memory_order_relaxed);
+	// nsd_set_debug_fill (tests): everything this launch is about to write -
+	// records, pool, workspace - filled with the byte first, ahead of all the
+	// launch queues (the sample's pair memset, zero_tiles, the kernels), so a
+	// store that never happens leaves the fill and not an earlier launch's
+	// value.  Not into a capturing stream (a graph replays its own nodes
+	// only; the caller fills before a replay).  ext_used and the counters
+	// accumulate and stay.
+	const int fill = g_debug_fill.load(std::memory_order_relaxed);
+	if (fill >= 0) {
+		hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+		if (hipStreamIsCapturing(stream, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone) {
+			if (hipMemsetAsync(d_rec, fill, (size_t)n * (compact ? sizeof(nsd_crec) : sizeof(nsd_rec)), stream) != hipSuccess ||
+			    (d_ext && ext_words && hipMemsetAsync(d_ext, fill, (size_t)ext_words * 4, stream) != hipSuccess) ||
+			    (d_ws && hipMemsetAsync(d_ws, fill, nsd_launch_workspace_bytes(n), stream) != hipSuccess))
+				return -2;
+		}
+	}
 	unsigned long long *const pair = d_ws ? (unsigned long long *)((uint8_t *)d_ws + sched_pair_at(n)) : nullptr;
 	const Plan plan = sched_plan(n, mi != 2 ? pair : nullptr, d_counters, stream);
 	const int s_cus = plan.cus;

@@ -126,7 +126,7 @@ ABI_SYMBOLS = ["dissector_init_all", "dissector_entry_point", "dissector_cleanup
                "nsd_pipe_submit_compact", "nsd_format_range_compact", "nsd_set_schedule",
                "nsd_last_schedule", "nsd_format_frame_hdr", "nsd_format_range_compact_fh",
                "nsd_pcap_read_batch_fh", "nsd_t3_block_desc_fh", "nsd_pcap_index", "nsd_set_grid_cap",
-               "nsd_set_record_ring"]
+               "nsd_set_record_ring", "nsd_set_debug_fill"]
 
 # struct sockaddr_ll (nsd_sll_t), one per packet for LINKTYPE_LINUX_SLL batches
 SLL_DTYPE = np.dtype([("family", "<u2"), ("protocol", ">u2"), ("ifindex", "<i4"), ("hatype", "<u2"),
@@ -263,6 +263,7 @@ def lib():
                 ("nsd_pcap_read_batch_fh", ctypes.c_long, [_vp, _vp, _sz, _vp, _vp, _vp, _u32]),
                 ("nsd_t3_block_desc_fh", ctypes.c_long, [_vp, _sz, _int, _int, _vp, _vp, _vp, _u32]),
                 ("nsd_pcap_index", ctypes.c_long, [ctypes.c_char_p, _u64, _int, _vp, _vp, _sz]),
+                ("nsd_set_debug_fill", _int, [_int]),
                 ("nsd_last_schedule", _int, [])):
             if hasattr(L, name):
                 getattr(L, name).restype = res
@@ -308,6 +309,15 @@ def set_grid_cap(blocks):
     if rc < 0:
         raise ValueError(f"bad grid cap {blocks}")
     return rc
+
+
+def set_debug_fill(byte):
+    """Fill what every batch walk is about to write (records, ext pool,
+    workspace) with `byte` (0..255) before the launch, or stop doing so (-1,
+    the default); returns the previous value (nsd_set_debug_fill, tests)."""
+    if not -1 <= byte <= 255:      # (the library's NSD_ERR_ARG is -1, as "off" is)
+        raise ValueError(f"bad debug fill {byte}")
+    return lib().nsd_set_debug_fill(byte)
 
 
 def last_schedule():
@@ -363,9 +373,10 @@ def dissect_device(frames, desc, mode=PRINT_NORM, linktype=LINKTYPE_EN10MB, rec=
 
 
 def dissect_device_compact(frames, desc, mode=PRINT_NORM, linktype=LINKTYPE_EN10MB, crec=None, ext=None,
-                           ext_used=None, counters=None, stream=None, workspace=None, sll=None):
+                           ext_used=None, counters=None, stream=None, workspace=None, sll=None, ext_words=None):
     """dissect_device writing compact 8-byte records (nsd_crec).  Returns
-    (crec u8[n*8], ext, ext_used, counters) as cuda tensors."""
+    (crec u8[n*8], ext, ext_used, counters) as cuda tensors.  ext_words: the
+    pool size given to the library when it is not the whole of `ext`."""
     import torch
     n = desc.numel()
     dev = desc.device
@@ -378,6 +389,7 @@ def dissect_device_compact(frames, desc, mode=PRINT_NORM, linktype=LINKTYPE_EN10
     if counters is None:
         counters = torch.zeros(NCOUNTERS, dtype=torch.int64, device=dev)
     assert ext.element_size() == 4, "the ext pool is u32 words"
+    assert ext_words is None or 0 <= ext_words <= ext.numel()
     if stream is None:
         stream = torch.cuda.current_stream(dev).cuda_stream
     L = lib()
@@ -385,7 +397,8 @@ def dissect_device_compact(frames, desc, mode=PRINT_NORM, linktype=LINKTYPE_EN10
         workspace = torch.empty(L.nsd_workspace_bytes(n), dtype=torch.uint8, device=dev)
     rc = L.nsd_dissect_device_compact(frames.data_ptr(), desc.data_ptr(),
                                       None if sll is None else sll.data_ptr(), n, linktype, mode,
-                                      crec.data_ptr(), ext.data_ptr(), ext.numel(), ext_used.data_ptr(),
+                                      crec.data_ptr(), ext.data_ptr(),
+                                      ext.numel() if ext_words is None else ext_words, ext_used.data_ptr(),
                                       counters.data_ptr(), workspace.data_ptr(), stream)
     _check(rc, "nsd_dissect_device_compact")
     return crec, ext, ext_used, counters

@@ -9,7 +9,12 @@ import subprocess
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+try:                             # (bench.py and smoke() import this module without pytest)
+    import pytest
+except ImportError:
+    pytest = None
+
+ROOT =os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ORACLE_DIR = os.path.join(ROOT, "oracle")
 REF_BIN = os.path.join(ORACLE_DIR, "_ref", "nsref")
 SYNTH_SO = os.path.join(ROOT, "tools", "libnsdsynth.so")
@@ -38,6 +43,27 @@ def build_native(quiet=True):
 
 _synth = None
 _oracle = None
+
+FILL = 0xA5                      # the byte device_fill poisons with
+FILL32 = 0xA5A5A5A5
+
+
+def _fixture(f):
+    return f if pytest is None else pytest.fixture(f)
+
+
+@_fixture
+def device_fill():
+    """Every batch walk of the test first fills its records, ext pool and
+    workspace with FILL (nsd_set_debug_fill), so a store the kernel never
+    makes compares as 0xA5.. and not as the value an earlier launch left at
+    the same address (the library's buffers and torch's caching allocator
+    hand the same memory to run after run).  A module that uses it imports
+    it: `from nsd_testlib import device_fill`."""
+    import nsd
+    prev = nsd.set_debug_fill(FILL)
+    yield FILL
+    nsd.set_debug_fill(prev)
 
 
 def synth():

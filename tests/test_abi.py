@@ -57,6 +57,37 @@ def test_record_ring_knob():
         nsd.set_record_ring(prev)
 
 
+def test_debug_fill_returns_previous_value():
+    """nsd_set_debug_fill: -1 off (the default) or a byte 0..255; each call
+    returns the value the one before it set."""
+    L = nsd.lib()
+    prev = L.nsd_set_debug_fill(0xA5)
+    try:
+        assert prev == -1                              # off by default
+        assert L.nsd_set_debug_fill(0) == 0xA5
+        assert L.nsd_set_debug_fill(255) == 0
+        assert L.nsd_set_debug_fill(-1) == 255
+        assert nsd.set_debug_fill(0x5A) == -1          # the binding's wrapper
+        assert nsd.set_debug_fill(-1) == 0x5A
+    finally:
+        L.nsd_set_debug_fill(prev)
+
+
+def test_debug_fill_rejects_other_arguments():
+    """Anything but -1..255 is NSD_ERR_ARG and leaves the setting as it was;
+    the wrapper raises before the call."""
+    L = nsd.lib()
+    prev = L.nsd_set_debug_fill(7)
+    try:
+        for bad in (-2, 256, 0x1A5, -(1 << 31), (1 << 31) - 1):
+            assert L.nsd_set_debug_fill(bad) == -1     # NSD_ERR_ARG
+            with pytest.raises(ValueError):
+                nsd.set_debug_fill(bad)
+        assert L.nsd_set_debug_fill(7) == 7            # still set
+    finally:
+        L.nsd_set_debug_fill(prev)
+
+
 def test_library_carries_the_tree_source_hash():
     """The library names the sources it was built from (nsd_build_info's
     `sources` hash, the Makefile's SRCHASH) and they are this tree's: what

@@ -21,6 +21,7 @@ import pytest
 import edge_cases as E
 import nsd
 import nsd_testlib as T
+from nsd_testlib import device_fill  # noqa: F401  (fixture: nsd_set_debug_fill(0xA5) around each test)
 
 ACCEPT = 0xFFFFFFFF
 
@@ -352,6 +353,18 @@ def test_device_random_programs():
             assert np.array_equal(bp.filter_batch(sf, sd), oracle_batch(p, sf, sd)), t
 
 
+def _poisoned(torch, n):
+    """The filter launcher's outputs and workspace as tensors filled with 0xA5
+    (it is not nsd_launch_dissect_rec: nsd_set_debug_fill does not reach it),
+    so a verdict, an accepted descriptor or a block count the kernels never
+    write cannot pass for the one an earlier launch left in the same block of
+    torch's caching allocator."""
+    def full(nbytes):
+        return torch.full((nbytes,), T.FILL, dtype=torch.uint8, device="cuda")
+    return {"verdict": full(4 * max(n, 1)).view(torch.int32), "out": full(8 * max(n, 1)).view(torch.int64),
+            "workspace": full(nsd.lib().nsd_bpf_workspace_bytes(n))}
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("cfg,n", [(T.SYN_IMIX, 100000), (T.SYN_UDP64, 3000), (T.SYN_IPV6X, 1),
                                    (T.SYN_IMIX, 1024), (T.SYN_IMIX, 1025), (T.SYN_IMIX, 3 << 20),
@@ -366,7 +379,7 @@ def test_device_compaction(cfg, n):
     bp = nsd.BpfProgram(p)
     f = torch.from_numpy(frames).cuda()
     d = torch.from_numpy(desc.view(np.int64)).cuda()
-    verdict, out, count = bp.filter_device(f, d, compact=True)
+    verdict, out, count = bp.filter_device(f, d, compact=True, **_poisoned(torch, n))
     torch.cuda.synchronize()
     want = oracle_batch(p, frames, desc)
     assert np.array_equal(verdict.cpu().numpy().view(np.uint32), want)
@@ -376,6 +389,7 @@ def test_device_compaction(cfg, n):
 
 
 @pytest.mark.gpu
+@pytest.mark.usefixtures("device_fill")
 def test_device_filter_then_dissect():
     """Capture-loop order (read_pcap: filter, then dissect the survivors): the
     compacted descriptors feed the dissect kernels; records and counters
@@ -385,7 +399,7 @@ def test_device_filter_then_dissect():
     bp = nsd.BpfProgram(P_TCP)
     f = torch.from_numpy(frames).cuda()
     d = torch.from_numpy(desc.view(np.int64)).cuda()
-    _, out, count = bp.filter_device(f, d, compact=True)
+    _, out, count = bp.filter_device(f, d, compact=True, **_poisoned(torch, len(desc)))
     torch.cuda.synchronize()
     k = int(count.item())
     rec, _, _, counters = nsd.dissect_device(f, out[:k])

@@ -6,8 +6,9 @@ import pytest
 import edge_cases
 import nsd
 import nsd_testlib as T
+from nsd_testlib import device_fill  # noqa: F401  (fixture: nsd_set_debug_fill(0xA5) around each test)
 
-pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("schedule_small")]
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("schedule_small", "device_fill")]
 
 MODES = [T.PRINT_NORM, T.PRINT_LESS, T.PRINT_HEX]
 
@@ -630,7 +631,10 @@ def test_graph_capture_and_replay(compact, schedule_small):
     over new frames in the same buffers gives the oracle's records and
     counters each time (C2, C3, C4 batches through one graph), under both
     schedules (an adaptive launch under capture keeps the plan it has and is
-    never the sample: no event query or host copy inside the graph)."""
+    never the sample: no event query or host copy inside the graph).
+    Records, pool and workspace are filled with 0xA5 before every replay:
+    the graph's own nodes (zero_tiles, the kernels) must set up again
+    whatever of the workspace the kernels read, and write every record."""
     import torch
     n = 8192
     batches = [T.make_batch(cfg, n, seed=T.SEED + k) for k, cfg in
@@ -674,6 +678,11 @@ def test_graph_capture_and_replay(compact, schedule_small):
         walk()
     for k in range(len(batches)):
         load(k)
+        # (a captured launch is not filled by the launcher: poison what the
+        # replay is about to write here, the workspace included - the graph
+        # itself must set up again whatever of it the kernels read)
+        for t in (rec, ext, ws):
+            t.view(torch.uint8).fill_(T.FILL)
         g.replay()
         torch.cuda.synchronize()
         f, d = batches[k]
@@ -722,3 +731,267 @@ def test_cut_sweep_live_tails(mode):
     assert len(desc) > 20000
     _check(frames, desc, mode)
     _check_compact(frames, desc, mode)
+
+
+# ---- the record ring's eviction path, by construction ----------------------------------
+_EVICT_SLOW = ("slow10", "slow14", "slow10_leaf", "slow14_leaf")
+_EVICT_TILES, _EVICT_TAIL = 72, 17
+_EVICT_BATCH = []
+
+
+def _evict_packet(kind, rnd):
+    """One frame of the eviction batch (test_ring_eviction_by_construction's
+    table): `plain` Ethernet / IPv4 / UDP, 64 bytes; `quick` / `quick7` IPv6
+    with one / four 8-byte extension headers and UDP (4 / 7 layers);
+    `slow10` / `slow14` IPv6 with seven / eleven 128-byte extension headers
+    (hdr ext len 15) and UDP (10 / 14 layers, the transport header at byte
+    950 / 1462); `*_leaf` the same chains ending in an ICMPv6 neighbour
+    solicitation, a host-rendered leaf."""
+    E = edge_cases
+    if kind == "plain":
+        return E.eth(0x0800) + E.ipv4(17, 30, ttl=rnd.randrange(1, 255)) + \
+            E.udp(sport=rnd.randrange(1024, 65536), payload=bytes(rnd.randrange(256) for _ in range(22)))
+    nhdr, hl = {"quick": (1, 0), "quick7": (4, 0)}.get(kind, (11 if "14" in kind else 7, 15))
+    if kind.endswith("_leaf"):
+        last = 58
+        tail = bytes([135, 0]) + E.be16(0xBEEF) + E.be32(0) + bytes.fromhex("fe800000000000000211223344556677") + \
+            bytes([1, 1]) + bytes.fromhex("3cfdfe000002")
+    else:
+        last = 17
+        tail = E.udp(sport=rnd.randrange(1024, 65536),
+                     payload=bytes(rnd.randrange(256) for _ in range(rnd.randrange(9))))
+    ids = [0 if j % 2 == 0 else 60 for j in range(nhdr)]      # Hop-by-Hop, DestOpts, ..
+    body = b""
+    for j in range(nhdr):
+        nh = ids[j + 1] if j + 1 < nhdr else last
+        # options: one PadN over the whole header (type 1, its length, zeros)
+        room = (hl + 1) * 8 - 2
+        body += bytes([nh, hl]) + bytes([1, room - 2]) + bytes(room - 2)
+    body += tail
+    return E.eth(0x86DD) + E.ipv6(ids[0], len(body), flow=rnd.randrange(1 << 20)) + body
+
+
+def _evict_batch(seed=17):
+    """(frames, desc, kinds): the batch of test_ring_eviction_by_construction,
+    built once and never written.  72 full tiles and a last tile of 17
+    packets (4,625 packets, align 2).  Every full tile: four slow packets, at
+    lanes 0 and 63 and two seeded-random lanes, their kinds cycled (slow
+    packet k of tile t is kind (t + k) % 4, so every kind sits at lane 0 and
+    at lane 63 somewhere); six to eight quick / quick7 packets at random
+    lanes; plain packets elsewhere.  The last tile: two slow packets (lanes 0
+    and 16) and three quick ones."""
+    if not _EVICT_BATCH:
+        import random
+        rnd = random.Random(seed)
+        pkts, kinds = [], []
+        for t in range(_EVICT_TILES + 1):
+            width = 64 if t < _EVICT_TILES else _EVICT_TAIL
+            lanes = ["plain"] * width
+            free = list(range(1, width - 1))
+            rnd.shuffle(free)
+            if t < _EVICT_TILES:
+                slow = sorted([0, 63] + [free.pop(), free.pop()])
+                nquick = rnd.randint(6, 8)
+            else:
+                slow, nquick = [0, width - 1], 3
+            for k, lane in enumerate(slow):
+                lanes[lane] = _EVICT_SLOW[(t + k) % 4]
+            for _ in range(nquick):
+                lanes[free.pop()] = rnd.choice(["quick", "quick7"])
+            for kind in lanes:
+                pkts.append(_evict_packet(kind, rnd))
+                kinds.append(kind)
+        frames, desc = T.batch_from_packets(pkts, align=2)
+        frames.setflags(write=False)
+        desc.setflags(write=False)
+        _EVICT_BATCH.append((frames, desc, np.array(kinds)))
+    return _EVICT_BATCH[0]
+
+
+def _evict_preconditions(frames, desc, kinds, mode):
+    """What test_ring_eviction_by_construction's argument needs of the batch,
+    from the oracle's 16-byte records and entries alone (no GPU)."""
+    n = len(desc)
+    assert n == _EVICT_TILES * 64 + _EVICT_TAIL == 4625
+    orec, oext, _, _ = T.oracle_records(frames, desc, mode=mode)
+    want, wpool = nsd.compact_of(orec, oext)
+    slow = np.char.startswith(kinds, "slow")
+    for i in np.nonzero(slow)[0]:
+        ids, offs = _chain(orec, oext, i)
+        assert len(ids) == (14 if "14" in kinds[i] else 10), (i, kinds[i], ids)
+        # at least 7 consecutive layer starts, each >= 128 bytes (NSD_WIN2) after the one before
+        run = best = 0
+        for a, b in zip(offs, offs[1:]):
+            run = run + 1 if b - a >= 128 else 0
+            best = max(best, run)
+        assert best >= 7, (i, kinds[i], offs)
+    # every full tile defers 4..16 packets (data_off > 64: the suite's proxy for "deferred")
+    far = (orec["data_off"] > 64)[:_EVICT_TILES * 64].reshape(_EVICT_TILES, 64).sum(axis=1)
+    assert far.min() >= 4 and far.max() <= 16, (far.min(), far.max())
+    assert (slow[:_EVICT_TILES * 64].reshape(_EVICT_TILES, 64).sum(axis=1) == 4).all()
+    assert slow[_EVICT_TILES * 64:].sum() == 2
+    for k in range(4):   # every slow kind at lane 0 and at lane 63
+        assert (kinds[0:_EVICT_TILES * 64:64] == _EVICT_SLOW[k]).any()
+        assert (kinds[63:_EVICT_TILES * 64:64] == _EVICT_SLOW[k]).any()
+    s10 = (kinds == "slow10") | (kinds == "slow10_leaf")
+    s14 = (kinds == "slow14") | (kinds == "slow14_leaf")
+    assert ((want["nlayers"][s10] >= 7) & (want["nlayers"][s10] <= 12)).all()      # a side word
+    assert (want["nlayers"][kinds == "quick7"] == 7).all()
+    deep = ((want["nflags"] & 7) == 7) & (want["nlayers"] == 0)
+    assert np.array_equal(deep, s14) and (want["chain"][s14] != 0xFFFFFFFF).all()  # an entry
+    # the leaf kinds are host-rendered and only slow14_leaf records its leaf's
+    # end (slow10_leaf's side word holds ids) - in PRINT_NORM: print_less
+    # renders no ICMPv6 body, so there the kinds are plain 10 / 14-layer chains
+    norm = mode == T.PRINT_NORM
+    leaf = np.char.endswith(kinds, "_leaf")
+    assert np.array_equal((want["nflags"] & nsd.F_HOST) != 0, leaf & norm)
+    assert np.array_equal((want["nflags"] & nsd.F_LEAF_END) != 0, (kinds == "slow14_leaf") & norm)
+    assert ((want["nflags"] & nsd.F_OVERFLOW) == 0).all()
+    return orec
+
+
+@pytest.mark.parametrize("schedule_small", ["fused"], indirect=True)    # (the test sets its own schedules)
+@pytest.mark.parametrize("ring", ["ring", "noring"])
+@pytest.mark.parametrize("grid", [1, 3, 8, 0])
+@pytest.mark.parametrize("mode", [T.PRINT_NORM, T.PRINT_LESS])
+def test_ring_eviction_by_construction(mode, grid, ring):
+    """The record ring's eviction path (ring_turn with `held` lanes, then
+    ring_put's direct stores of record and side word), reached by
+    construction rather than by luck, and compared with the device outputs
+    poisoned (0xA5 in the tensors passed in, and the launcher's fill on).
+
+    The batch (_evict_batch): per full tile four slow packets - IPv6 chains of
+    seven or eleven 128-byte extension headers - a few quick ones and plain
+    packets.  Why a ring build must evict on it:
+      - a walker's window is at most NSD_WIN2 = 128 bytes, and with no
+        deferred packet waiting for a walker (`!more`) a tile visit runs one
+        session and carries the suspended walkers to the next tile; a slow
+        packet's headers start 128 bytes apart, so it needs at least seven
+        sessions, i.e. seven tile visits;
+      - at most 4 slow x 9 tiles + 12 packets are in flight per wave, fewer
+        than 64 walkers: packets never wait, so a visit is one session;
+      - every tile has deferrals, so every tile opens a ring slot, and the
+        two slots alternate;
+      - hence on any wave that walks three tiles in a row, the third tile's
+        ring_turn finds its slot's old tile with packets still on walkers:
+        the eviction store with `held` lanes.  Those packets later finish
+        through ring_put's direct branch, and for slow10 their side word goes
+        with them (slow14: an entry; the leaf kinds, host-rendered in
+        PRINT_NORM: the leaf pass, which writes slow14_leaf's end into entry
+        word 2 and has no end to record for slow10_leaf);
+      - 73 tiles over grid 1's 4 waves, grid 3's 12 and grid 8's 32 are more
+        than two per wave: by pigeonhole some wave walks three, whichever way
+        the dynamic tile sharing falls.
+    The last three full tiles and the partial tile hold slow packets too, so
+    the drain pass (`last`, the closing ring_turn) stores tiles still in the
+    ring and walkers store directly after it.
+    _evict_preconditions asserts the batch's side of this from the oracle
+    (tests/test_builders.py runs it without a GPU).  Ring off: the same
+    walkers carried across tiles without the ring; and the 16-byte form."""
+    import torch
+    frames, desc, kinds = _evict_batch()
+    _evict_preconditions(frames, desc, kinds, mode)
+    n = len(desc)
+    f = torch.from_numpy(np.array(frames)).cuda()
+    d = torch.from_numpy(np.array(desc).view(np.int64)).cuda()
+    crec = torch.full((n * nsd.CREC_BYTES,), T.FILL, dtype=torch.uint8, device="cuda")
+    ext = torch.full((nsd.ext_pool_words(n) * 4,), T.FILL, dtype=torch.uint8, device="cuda").view(torch.int32)
+    ws = torch.full((nsd.lib().nsd_workspace_bytes(n),), T.FILL, dtype=torch.uint8, device="cuda")
+    sched = nsd.set_schedule(nsd.SCHED_FUSED)
+    rprev = nsd.set_record_ring(nsd.RING_ON if ring == "ring" else nsd.RING_OFF)
+    cap = nsd.set_grid_cap(grid)
+    try:
+        assert nsd.set_debug_fill(T.FILL) == T.FILL      # the module's fixture keeps the fill on
+        _, _, used, cnt = nsd.dissect_device_compact(f, d, mode=mode, crec=crec, ext=ext, workspace=ws)
+        torch.cuda.synchronize()
+        assert nsd.last_schedule() == "fused"
+        got, pool = _compare_compact(crec, ext, used, cnt, frames, desc, mode)
+        _, rc = nsd.format_batch_compact(frames, desc, got, pool, mode=mode)
+        assert (rc == 0).all(), np.nonzero(rc)[0][:10]
+        _check(frames, desc, mode)
+    finally:
+        nsd.set_schedule(sched)
+        nsd.set_record_ring(rprev)
+        nsd.set_grid_cap(cap)
+
+
+# ---- compact records without side words ----------------------------------------------
+@pytest.mark.parametrize("pool", ["0", "n-1", "n+68"])
+def test_compact_pool_too_small(pool):
+    """test_ext_pool_full's compact counterpart (include/netsniff_dissect.h
+    "compact records"): the edge set and 200 packets of the eviction batch
+    with a pool of 0 or n - 1 words (no side words: side = ext_words >= n)
+    and of n + 68 words (side words, next to no room for entries).  A record
+    that needs a side word it cannot have carries NSD_F_OVERFLOW; without
+    side words no record carries NSD_F_LEAF_END; entries lie inside [n,
+    ext_words) and do not overlap; an entry that does not fit gives chain
+    0xFFFFFFFF with NSD_F_OVERFLOW; every other field equals
+    compact_of(oracle); and no pool word outside the side words and the
+    entries handed out has changed from the 0xA5 the test put there."""
+    import torch
+    ev_frames, ev_desc, _ = _evict_batch()
+    pkts = edge_cases.cases() + _packets_of(ev_frames, ev_desc)[:200]
+    frames, desc = T.batch_from_packets(pkts, align=2)
+    n = len(desc)
+    words = {"0": 0, "n-1": n - 1, "n+68": n + 68}[pool]
+    side = words >= n
+    guard = 256
+    f = torch.from_numpy(frames).cuda()
+    d = torch.from_numpy(desc.view(np.int64)).cuda()
+    ext = torch.full(((words + guard) * 4,), T.FILL, dtype=torch.uint8, device="cuda").view(torch.int32)
+    crec, _, used, cnt = nsd.dissect_device_compact(f, d, ext=ext, ext_words=words)
+    torch.cuda.synchronize()
+    got = crec.cpu().numpy().view(nsd.CREC_DTYPE)[:n]
+    dpool = ext.cpu().numpy().view(np.uint32)
+    orec, oext, ocnt, _ = T.oracle_records(frames, desc)          # full-capacity reference
+    want, wpool = nsd.compact_of(orec, oext)
+    need_side = want["nlayers"] != 0
+    deep = ((want["nflags"] & 7) == 7) & (want["nlayers"] == 0)
+    assert need_side.sum() > 10 and deep.sum() > 4 and ((want["nflags"] & nsd.F_LEAF_END) != 0).sum() > 10
+    # the flags each record must carry
+    flags = want["nflags"].copy()
+    if not side:
+        flags[need_side] |= nsd.F_OVERFLOW
+        flags &= ~np.uint8(nsd.F_LEAF_END)
+    touched = np.zeros(len(dpool), dtype=bool)     # words the contract lets the launch write
+    spans = []
+    for i in np.nonzero(deep)[0]:
+        slot = int(got[i]["chain"])
+        if int(want[i]["chain"]) == 0xFFFFFFFF:    # (a chain past 64 layers: no entry in any pool)
+            assert slot == 0xFFFFFFFF
+            continue
+        if slot == 0xFFFFFFFF:                     # the entry did not fit
+            flags[i] = (flags[i] | nsd.F_OVERFLOW) & ~np.uint8(nsd.F_LEAF_END)
+            continue
+        _, oids, _ = nsd.ext_entry(wpool, int(want[i]["chain"]))
+        end = slot + nsd.ext_words(len(oids))
+        assert n <= slot and end <= words, f"entry of packet {i} at [{slot}, {end}) outside [{n}, {words})"
+        gp, gids, goffs = nsd.ext_entry(dpool, slot)
+        assert gp == i and gids == oids and not any(goffs), f"ext chain differs at {i}"
+        if flags[i] & nsd.F_LEAF_END:
+            assert dpool[slot + 2] == wpool[int(want[i]["chain"]) + 2], f"leaf end differs at {i}"
+        spans.append((slot, end))
+        touched[slot:end] = True
+    spans.sort()
+    assert all(a[1] <= b[0] for a, b in zip(spans, spans[1:])), "entries overlap"
+    if not side:
+        assert not spans
+    bad = np.nonzero(got["nflags"] != flags)[0]
+    assert len(bad) == 0, f"nflags differ at {bad[:10]}: {got['nflags'][bad[:5]]} want {flags[bad[:5]]}"
+    for fld in ("ip_csum", "nlayers"):
+        assert np.array_equal(got[fld], want[fld]), fld
+    assert np.array_equal(got["chain"][~deep], want["chain"][~deep]), "chain ids differ"
+    if side:
+        # side words: the oracle's where a record has one; elsewhere untouched or zero (a ring tile's store)
+        has = need_side | (((flags & nsd.F_LEAF_END) != 0) & ~deep)
+        assert np.array_equal(dpool[:n][has], wpool[:n][has]), "side words differ"
+        assert np.isin(dpool[:n][~has], (0, T.FILL32)).all(), "a side word written for a record that has none"
+        touched[:n] = True
+    stray = np.nonzero(~touched & (dpool != T.FILL32))[0]
+    assert len(stray) == 0, f"pool words written outside the side words and entries: {stray[:10]}"
+    # the counters: the oracle's, and one NSD_CNT_OVERFLOW more per record that lost its chain here
+    lost = int(((flags & nsd.F_OVERFLOW) != 0).sum() - ((want["nflags"] & nsd.F_OVERFLOW) != 0).sum())
+    dcnt = cnt.cpu().numpy().view(np.uint64)
+    expect = ocnt.copy()
+    expect[nsd.CNT_OVERFLOW] += lost
+    assert np.array_equal(dcnt, expect), f"{nsd.unpack_counters(dcnt)} vs {nsd.unpack_counters(expect)}"

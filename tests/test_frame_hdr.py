@@ -22,6 +22,7 @@ import pytest
 
 import nsd
 import nsd_testlib as T
+from nsd_testlib import device_fill  # noqa: F401  (fixture: nsd_set_debug_fill(0xA5) around each test)
 import pcap_formats as PF
 import test_golden as TG
 
@@ -173,6 +174,7 @@ def fh_golden_cases():
 
 
 @pytest.mark.gpu
+@pytest.mark.usefixtures("device_fill")
 @pytest.mark.parametrize("name,mode,cols", fh_golden_cases())
 def test_replay_matches_reference_replay(name, mode, cols):
     """`netsniff-ng --in` on the device == the reference's read_pcap loop

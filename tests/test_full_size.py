@@ -16,9 +16,10 @@ import pytest
 
 import nsd
 import nsd_testlib as T
+from nsd_testlib import device_fill  # noqa: F401  (fixture: nsd_set_debug_fill(0xA5) around each test)
 from test_device_parity import _chain
 
-pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("schedule")]
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("schedule", "device_fill")]
 
 N = 1 << 24
 

@@ -13,6 +13,7 @@ import pytest
 import fuzz_cases
 import nsd
 import nsd_testlib as T
+from nsd_testlib import device_fill  # noqa: F401  (fixture: nsd_set_debug_fill(0xA5) around each test)
 
 N = 20000
 
@@ -42,7 +43,7 @@ def test_fuzz_formatter_vs_reference(tmp_path, mode):
 
 
 @pytest.mark.gpu
-@pytest.mark.usefixtures("schedule")
+@pytest.mark.usefixtures("schedule", "device_fill")
 @pytest.mark.parametrize("mode,align", [(T.PRINT_NORM, 16), (T.PRINT_LESS, 16), (T.PRINT_NORM, 1)])
 def test_fuzz_device_vs_oracle(mode, align):
     from test_device_parity import assert_same_records

@@ -15,6 +15,7 @@ import pytest
 
 import nsd
 import nsd_testlib as T
+from nsd_testlib import device_fill  # noqa: F401  (fixture: nsd_set_debug_fill(0xA5) around each test)
 import test_golden as TG
 
 G = T.GOLDEN
@@ -279,6 +280,7 @@ def frame_lines(path, mode, accepted=None):
 
 
 @pytest.mark.gpu
+@pytest.mark.usefixtures("device_fill")
 @pytest.mark.parametrize("mode", MODES)
 def test_replay_edge_matches_golden(tmp_path, mode):
     """`--in edge.pcap` end to end on the device: every record's frame header
@@ -296,6 +298,7 @@ def test_replay_edge_matches_golden(tmp_path, mode):
 
 
 @pytest.mark.gpu
+@pytest.mark.usefixtures("device_fill")
 def test_replay_read_paths(tmp_path, monkeypatch):
     """The replay's two readers give the same text: the mapped file (record
     index and bodies on the pool, several pool sizes and index windows), the
@@ -329,6 +332,7 @@ def test_replay_read_paths(tmp_path, monkeypatch):
 
 
 @pytest.mark.gpu
+@pytest.mark.usefixtures("device_fill")
 def test_concurrent_replays(tmp_path):
     """Two replays at once in one process (ctypes drops the GIL): one takes
     the cached staging and device pipe, the other builds its own set; both
@@ -356,6 +360,7 @@ def test_concurrent_replays(tmp_path):
 
 
 @pytest.mark.gpu
+@pytest.mark.usefixtures("device_fill")
 @pytest.mark.parametrize("mode", [T.PRINT_NORM, T.PRINT_LESS])
 def test_replay_wrapped_and_filtered(tmp_path, mode):
     """80-column tprintf wrap over the replay stream, and a BPF filter in
@@ -383,6 +388,7 @@ def test_replay_wrapped_and_filtered(tmp_path, mode):
 
 
 @pytest.mark.gpu
+@pytest.mark.usefixtures("device_fill")
 @pytest.mark.parametrize("key,cfg", [("udp64", T.SYN_UDP64), ("imix", T.SYN_IMIX), ("ipv6x", T.SYN_IPV6X)])
 @pytest.mark.parametrize("mode", [T.PRINT_NORM, T.PRINT_LESS])
 def test_replay_prefix_digest(tmp_path, key, cfg, mode):
@@ -450,6 +456,7 @@ def test_reader_sll_cooked_headers(tmp_path, endian):
 
 
 @pytest.mark.gpu
+@pytest.mark.usefixtures("device_fill")
 @pytest.mark.parametrize("mode", [T.PRINT_NORM, T.PRINT_LESS])
 def test_replay_sll_file(tmp_path, mode):
     """`--in` an SLL capture: each record's cooked header reaches the SLL
@@ -494,6 +501,7 @@ def _records(data, hdrsize, endian, ll=False):
 
 
 @pytest.mark.gpu
+@pytest.mark.usefixtures("device_fill")
 @pytest.mark.parametrize("fmt", ["usec", "usec_be", "nsec", "kuz", "bkm_be", "sll", "sll_be"])
 def test_replay_pcap_out(tmp_path, fmt):
     """`--in a.pcap --out b.pcap`: pcap_generic_push_fhdr's header for the

@@ -11,6 +11,7 @@ import pytest
 import edge_cases
 import nsd
 import nsd_testlib as T
+from nsd_testlib import device_fill  # noqa: F401  (fixture: nsd_set_debug_fill(0xA5) around each test)
 
 PACKET_HOST, PACKET_OUTGOING = 0, 4
 
@@ -77,6 +78,7 @@ def test_block_inconsistent():
 
 
 @pytest.mark.gpu
+@pytest.mark.usefixtures("device_fill")
 @pytest.mark.parametrize("mode", [T.PRINT_NORM, T.PRINT_LESS])
 def test_block_dissect_on_device(mode):
     from test_device_parity import assert_same_records
@@ -143,6 +145,7 @@ def test_live_ring_block_desc():
 
 
 @pytest.mark.gpu
+@pytest.mark.usefixtures("device_fill")
 @pytest.mark.parametrize("mode", [T.PRINT_NORM, T.PRINT_LESS])
 def test_live_ring_registered_through_pipe(mode):
     """The same ring on the GPU: each retired block is registered with
@@ -185,6 +188,7 @@ def test_live_ring_registered_through_pipe(mode):
 
 
 @pytest.mark.gpu
+@pytest.mark.usefixtures("device_fill")
 @pytest.mark.parametrize("mode", [T.PRINT_NORM, T.PRINT_LESS])
 def test_cooked_ring_through_pipe(mode):
     """A cooked (LINKTYPE_LINUX_SLL) ring: the block is the frame buffer, the

@@ -18,6 +18,7 @@ import pytest
 import edge_cases as E
 import nsd
 import nsd_testlib as T
+from nsd_testlib import device_fill  # noqa: F401  (fixture: nsd_set_debug_fill(0xA5) around each test)
 
 ADDR = bytes.fromhex("deadbeef01020304")
 
@@ -123,6 +124,7 @@ def test_tables_match_reference_dev_c():
 
 
 @pytest.mark.gpu
+@pytest.mark.usefixtures("device_fill")
 @pytest.mark.parametrize("mode", [T.PRINT_NORM, T.PRINT_LESS])
 def test_sll_device_vs_oracle(mode):
     from test_device_parity import assert_same_records
