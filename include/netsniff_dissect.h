@@ -674,6 +674,91 @@ int nsd_bpf_filter_device(const nsd_bpf_prog *prog, const uint8_t *d_frames,
 int nsd_bpf_filter_batch(const nsd_bpf_prog *prog, const uint8_t *frames, size_t frames_len,
 			 const nsd_desc_t *desc, uint32_t n, uint32_t *verdict);
 
+/* ---- flow table: per-flow statistics over dissected batches ----------------
+ * What flowtop shows per conversation (flowtop.c: struct flow_entry's
+ * per-flow packet and byte counters, read from conntrack's CTA_COUNTERS)
+ * aggregated on the device from a batch walk's 16-byte records: a hash table
+ * in HBM keyed by (src, dst, sport, dport, l3, l4), so a batch leaves the
+ * device as one row per flow.  Flows are unidirectional, src -> dst.
+ *
+ * Key of a packet (from its nsd_rec, its ext entry and its frame; bytes at
+ * offsets >= caplen read as zero, and the key reads at most the first
+ * NSD_MAX_CAPLEN bytes):
+ *   L3: the first layer of the chain whose id is NSD_OPS_IPV4 or
+ *       NSD_OPS_IPV6 (the outermost; NSD_OPS_IPV6_IN_IPV4 is none).  An IPv4
+ *       address fills src / dst bytes 0..3, the rest are zero.  A packet
+ *       without such a layer is not keyed (NSD_FLOW_ST_NOIP), nor is a record
+ *       with NSD_F_OVERFLOW or whose ext entry lies outside the pool given
+ *       (NSD_FLOW_ST_SKIPPED).
+ *   L4: the last layer of the chain; l4 is its ops id.  TCP, UDP and DCCP
+ *       give sport / dport (host order), every other layer 0 / 0; so does a
+ *       later IPv4 fragment (the L3's frag_off & 0x1fff != 0: the reference
+ *       still dispatches it to tcp, but the bytes are no TCP header).
+ *   tcp_flags: the OR of the TCP flag bytes (header byte 13) of the flow's
+ *       TCP packets that are no later fragments.
+ * stats: PKTS = KEYED + NOIP + SKIPPED; FULL (a subset of KEYED) are packets
+ * dropped because every slot was taken by other flows - a flow is in the
+ * table with all its packets or not at all; FLOWS = the flows in the table.
+ *
+ * nsd_flow_create: slots = the power of two >= 2 * max_flows (1 <= max_flows
+ * <= 2^30); all the table's device memory is allocated here, on the current
+ * device, and the table starts reset.  NULL without a GPU or memory.
+ * nsd_flow_update_device accumulates one dissected batch (device pointers,
+ * 16-byte records, d_rec 16-byte aligned; d_ext / ext_words the walk's pool):
+ * packet i counts as index base + i in first / last.  It only enqueues on
+ * `stream` (no allocation, no host synchronisation: graph-capturable like
+ * nsd_dissect_device_ws); n <= 0xFFFFFFF0.  The inputs must stay unchanged
+ * until the call's work has run.  Calls on one table must be ordered on one
+ * stream.
+ * nsd_flow_export_device packs the flows into d_flows (8-byte aligned) in
+ * unspecified order: *d_count = the number of flows, which may exceed `max`
+ * (only `max` rows are written); d_stats[NSD_FLOW_NSTATS] is overwritten.
+ * nsd_flow_export: to host memory, synchronous, sorted by `first` (unique per
+ * flow) ascending; returns the number of flows (the first `max` are written),
+ * stats may be NULL.
+ * nsd_flow_batch: host-memory convenience in the style of
+ * dissector_entry_batch (stage, walk, update, export); returns like
+ * nsd_flow_export.
+ * nsd_pcap_flows: read_pcap's loop (netsniff-ng.c:707-756: read a record,
+ * run the filter, dissect) with the flow table in the dissector's place: the
+ * file is read batch by batch with the pcap reader below, the optional BPF
+ * program applied with the device compaction (nsd_bpf_filter_device), the
+ * accepted packets walked and accumulated with base = the packet's index
+ * among the accepted packets of the file.  A record above NSD_MAX_CAPLEN is
+ * keyed from its first NSD_MAX_CAPLEN bytes and counts its whole caplen.
+ * Returns the packets fed or a negative NSD_ERR_*.  No text is produced.
+ * nsd_flow_cpu: the same aggregation on the host CPU over records already
+ * made (ext = the whole pool the records' slots index, trusted), sorted by
+ * `first`; for hosts without a GPU, and the in-product check of the key
+ * logic.  Returns the number of flows (FULL is always 0). */
+typedef struct nsd_flow {          /* 72 bytes; bytes 0..37 are the key */
+	uint8_t  src[16], dst[16];
+	uint16_t sport, dport;
+	uint8_t  l3, l4;           /* ops ids */
+	uint8_t  tcp_flags;        /* OR over the flow's packets */
+	uint8_t  rsvd;             /* 0 */
+	uint64_t pkts, bytes;      /* bytes = sum of caplen, as NSD_CNT_BYTES */
+	uint64_t first, last;      /* base + index of the flow's first / last packet */
+} nsd_flow;
+enum { NSD_FLOW_ST_PKTS, NSD_FLOW_ST_KEYED, NSD_FLOW_ST_NOIP, NSD_FLOW_ST_SKIPPED,
+       NSD_FLOW_ST_FULL /* packets dropped: every slot taken */, NSD_FLOW_ST_FLOWS, NSD_FLOW_NSTATS = 8 };
+typedef struct nsd_flow_table nsd_flow_table;
+nsd_flow_table *nsd_flow_create(uint32_t max_flows);
+void nsd_flow_destroy(nsd_flow_table *t);
+uint32_t nsd_flow_slots(const nsd_flow_table *t);
+int nsd_flow_reset(nsd_flow_table *t, void *stream);
+int nsd_flow_update_device(nsd_flow_table *t, const uint8_t *d_frames, const nsd_desc_t *d_desc,
+			   uint32_t n, const nsd_rec *d_rec, const uint32_t *d_ext, uint32_t ext_words,
+			   uint64_t base, void *stream);
+int nsd_flow_export_device(nsd_flow_table *t, nsd_flow *d_flows, uint32_t max, uint32_t *d_count,
+			   uint64_t *d_stats, void *stream);
+long nsd_flow_export(nsd_flow_table *t, nsd_flow *flows, uint32_t max, uint64_t *stats);
+long nsd_flow_batch(const uint8_t *frames, size_t frames_len, const nsd_desc_t *desc, uint32_t n,
+		    int linktype, int mode, nsd_flow *flows, uint32_t max, uint64_t *stats);
+long nsd_pcap_flows(const char *path, int mode, const struct nsd_bpf_prog *filter, nsd_flow_table *t);
+long nsd_flow_cpu(const uint8_t *frames, const nsd_desc_t *desc, uint32_t n, const nsd_rec *rec,
+		  const uint32_t *ext, uint64_t base, nsd_flow *flows, uint32_t max, uint64_t *stats);
+
 /* Pinned host memory for the pipe's buffers. */
 void *nsd_host_alloc(size_t len);
 void nsd_host_free(void *ptr);

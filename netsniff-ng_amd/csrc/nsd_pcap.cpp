@@ -674,6 +674,86 @@ extern "C" long nsd_replay_pcap(const char *path, int mode, const nsd_bpf_prog *
 	return nsd_replay_pcap_out(path, mode, filter, out_fd, cols, counters, threads, -1);
 }
 
+// ---- flows of a capture file (nsd_flow.hip) -----------------------------------
+extern "C" __attribute__((visibility("hidden"))) long nsd_flow_feed_host(nsd_flow_table *t, const uint8_t *frames,
+									  size_t frames_len, const nsd_desc_t *desc,
+									  const nsd_sll_t *sll, uint32_t n, int linktype,
+									  int mode, const nsd_bpf_prog *filter, uint64_t base);
+extern "C" __attribute__((visibility("hidden"))) int nsd_flow_feed_records(nsd_flow_table *t, const uint8_t *frames,
+									    size_t frames_len, const nsd_desc_t *desc,
+									    uint32_t n, const nsd_rec *rec,
+									    const uint32_t *ext, uint32_t ext_words,
+									    uint64_t base);
+
+// read_pcap's loop (netsniff-ng.c:707-756: next record, bpf_run_filter, then
+// the dissector) with the flow table where the dissector's text would be:
+// batches of the reader go through the device filter / walk / update; a
+// record no batch carries is filtered and walked by the per-packet path over
+// its first NSD_MAX_CAPLEN bytes and added with its whole caplen.
+extern "C" long nsd_pcap_flows(const char *path, int mode, const nsd_bpf_prog *filter, nsd_flow_table *t)
+{
+	if (!path || !t || mode < PRINT_NORM || mode > PRINT_NONE)
+		return NSD_ERR_ARG;
+	nsd_pcap *p = nsd_pcap_open(path);
+	if (!p)
+		return NSD_ERR_ARG;
+	const int lt = (int)p->linktype;
+	const bool has_ll = p->ll_extra != 0 || p->linktype == LT_LINUX_SLL || p->linktype == bswap32(LT_LINUX_SLL);
+	constexpr size_t CAP = 16u << 20;
+	constexpr uint32_t MAX_N = 1u << 16;
+	std::vector<uint8_t> frames(CAP), big;
+	std::vector<nsd_desc_t> desc(MAX_N);
+	std::vector<nsd_sll_t> sll(MAX_N);
+	uint64_t fed = 0;
+	long rc = NSD_OK;
+	while (rc == NSD_OK) {
+		const long n = read_batch(p, frames.data(), CAP, desc.data(), sll.data(), nullptr, MAX_N, nullptr, nullptr,
+					  nullptr);
+		if (n == 0)
+			break;
+		if (n > 0) {
+			size_t used = 0;
+			for (long j = 0; j < n; j++) {
+				const size_t e = NSD_DESC_OFF(desc[j]) + NSD_DESC_CAPLEN(desc[j]);
+				used = e > used ? e : used;
+			}
+			const long k = nsd_flow_feed_host(t, frames.data(), used, desc.data(), has_ll ? sll.data() : nullptr,
+							  (uint32_t)n, lt, mode, filter, fed);
+			if (k < 0)
+				rc = k;
+			else
+				fed += (uint64_t)k;
+			continue;
+		}
+		if (n != NSD_ERR_CAPLEN) {
+			rc = n;
+			break;
+		}
+		nsd_sll_t ll;
+		const long caplen = read_one(p, big, &ll, nullptr, nullptr);
+		if (caplen <= 0)
+			break;
+		const nsd_desc_t d = NSD_DESC(0, caplen);
+		if (filter) {
+			uint32_t v = 0;
+			rc = nsd_bpf_filter_batch(filter, big.data(), (size_t)caplen, &d, 1, &v);
+			if (rc != NSD_OK || !v)
+				continue;
+		}
+		const uint32_t head = (uint32_t)caplen < NSD_MAX_CAPLEN ? (uint32_t)caplen : NSD_MAX_CAPLEN;
+		nsd_rec rec;
+		uint32_t ext[NSD_EXT_WORDS(NSD_EXT_MAX_LAYERS)] = { 0 };
+		rc = nsd_walk_packet_cpu(big.data(), head, lt, mode, has_ll ? &ll : nullptr, &rec, ext,
+					 NSD_EXT_WORDS(NSD_EXT_MAX_LAYERS), nullptr);
+		if (rc == NSD_OK)
+			rc = nsd_flow_feed_records(t, big.data(), head, &d, 1, &rec, ext, NSD_EXT_WORDS(NSD_EXT_MAX_LAYERS), fed);
+		if (rc == NSD_OK)
+			fed++;
+	}
+	nsd_pcap_close(p);
+	return rc == NSD_OK ? (long)fed : rc;
+}
+
 static bool write_all(int fd, const void *buf, size_t n)
 {
 	const uint8_t *w = (const uint8_t *)buf;

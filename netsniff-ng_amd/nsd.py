@@ -126,7 +126,9 @@ ABI_SYMBOLS = ["dissector_init_all", "dissector_entry_point", "dissector_cleanup
                "nsd_pipe_submit_compact", "nsd_format_range_compact", "nsd_set_schedule",
                "nsd_last_schedule", "nsd_format_frame_hdr", "nsd_format_range_compact_fh",
                "nsd_pcap_read_batch_fh", "nsd_t3_block_desc_fh", "nsd_pcap_index", "nsd_set_grid_cap",
-               "nsd_set_record_ring", "nsd_set_debug_fill"]
+               "nsd_set_record_ring", "nsd_set_debug_fill", "nsd_flow_create", "nsd_flow_destroy",
+               "nsd_flow_slots", "nsd_flow_reset", "nsd_flow_update_device", "nsd_flow_export_device",
+               "nsd_flow_export", "nsd_flow_batch", "nsd_pcap_flows", "nsd_flow_cpu"]
 
 # struct sockaddr_ll (nsd_sll_t), one per packet for LINKTYPE_LINUX_SLL batches
 SLL_DTYPE = np.dtype([("family", "<u2"), ("protocol", ">u2"), ("ifindex", "<i4"), ("hatype", "<u2"),
@@ -137,6 +139,14 @@ LINKTYPE_NETLINK = 253
 # nsd_frame_hdr_t: the tpacket header fields show_frame_hdr prints
 FH_DTYPE = np.dtype([("len", "<u4"), ("sec", "<u4"), ("nsec", "<u4"), ("status", "<u4"), ("vlan_tci", "<u4"),
                      ("vlan_tpid", "<u2"), ("v3", "u1"), ("reserved", "u1")])
+
+# nsd_flow: one row of a flow table (bytes 0..37 are the key)
+FLOW_DTYPE = np.dtype([("src", "u1", (16,)), ("dst", "u1", (16,)), ("sport", "<u2"), ("dport", "<u2"),
+                       ("l3", "u1"), ("l4", "u1"), ("tcp_flags", "u1"), ("rsvd", "u1"), ("pkts", "<u8"),
+                       ("bytes", "<u8"), ("first", "<u8"), ("last", "<u8")])
+FLOW_BYTES = 72
+FLOW_NSTATS = 8
+FLOW_ST_PKTS, FLOW_ST_KEYED, FLOW_ST_NOIP, FLOW_ST_SKIPPED, FLOW_ST_FULL, FLOW_ST_FLOWS = range(6)
 
 _lib = None
 _vp, _u32, _u64, _int, _sz = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int, ctypes.c_size_t
@@ -264,6 +274,16 @@ def lib():
                 ("nsd_t3_block_desc_fh", ctypes.c_long, [_vp, _sz, _int, _int, _vp, _vp, _vp, _u32]),
                 ("nsd_pcap_index", ctypes.c_long, [ctypes.c_char_p, _u64, _int, _vp, _vp, _sz]),
                 ("nsd_set_debug_fill", _int, [_int]),
+                ("nsd_flow_create", _vp, [_u32]),
+                ("nsd_flow_destroy", None, [_vp]),
+                ("nsd_flow_slots", _u32, [_vp]),
+                ("nsd_flow_reset", _int, [_vp, _vp]),
+                ("nsd_flow_update_device", _int, [_vp, _vp, _vp, _u32, _vp, _vp, _u32, _u64, _vp]),
+                ("nsd_flow_export_device", _int, [_vp, _vp, _u32, _vp, _vp, _vp]),
+                ("nsd_flow_export", ctypes.c_long, [_vp, _vp, _u32, _vp]),
+                ("nsd_flow_batch", ctypes.c_long, [_vp, _sz, _vp, _u32, _int, _int, _vp, _u32, _vp]),
+                ("nsd_pcap_flows", ctypes.c_long, [ctypes.c_char_p, _int, _vp, _vp]),
+                ("nsd_flow_cpu", ctypes.c_long, [_vp, _vp, _u32, _vp, _vp, _u64, _vp, _u32, _vp]),
                 ("nsd_last_schedule", _int, [])):
             if hasattr(L, name):
                 getattr(L, name).restype = res
@@ -704,6 +724,119 @@ class BpfProgram:
 
     def __del__(self):
         self.close()
+
+
+# ---- flow table (nsd_flow_*: per-flow statistics over dissected batches) ---------------
+class FlowTable:
+    """A flow table on the current device (nsd_flow_create): slots = the power
+    of two >= 2 * max_flows.  update() accumulates dissected batches (cuda
+    tensors, as dissect_device returns them) on torch's current stream;
+    raises NsdError without a GPU."""
+
+    def __init__(self, max_flows):
+        self.L = lib()
+        self.h = self.L.nsd_flow_create(max_flows)
+        if not self.h:
+            raise NsdError("nsd_flow_create failed (bad size, no memory or no GPU)")
+        self.slots = self.L.nsd_flow_slots(self.h)
+
+    @staticmethod
+    def _stream(stream, dev=None):
+        if stream is not None:
+            return stream
+        import torch
+        return torch.cuda.current_stream(dev).cuda_stream
+
+    def reset(self, stream=None):
+        _check(self.L.nsd_flow_reset(self.h, self._stream(stream)), "nsd_flow_reset")
+
+    def update(self, frames, desc, rec, ext=None, base=0, n=None, stream=None):
+        """One dissected batch: frames / desc as given to the walk, rec u8[n*16]
+        and ext (the pool, or None) as it returned them; packet i counts as
+        base + i.  n: the packets of desc to take (default all)."""
+        n = desc.numel() if n is None else n
+        words = 0 if ext is None else ext.numel()
+        rc = self.L.nsd_flow_update_device(self.h, frames.data_ptr(), desc.data_ptr(), n, rec.data_ptr(),
+                                           None if ext is None else ext.data_ptr(), words, base,
+                                           self._stream(stream, desc.device))
+        _check(rc, "nsd_flow_update_device")
+
+    def export_device(self, max_flows=None, flows=None, count=None, stats=None, stream=None):
+        """(flows u8[max*72], count i32[1], stats i64[8]) cuda tensors; count
+        may exceed max (only max rows are written), order unspecified."""
+        import torch
+        if flows is None:
+            flows = torch.empty((self.slots if max_flows is None else max_flows) * FLOW_BYTES, dtype=torch.uint8,
+                                device="cuda")
+        if max_flows is None:
+            max_flows = flows.numel() // FLOW_BYTES
+        if count is None:
+            count = torch.zeros(1, dtype=torch.int32, device=flows.device)
+        if stats is None:
+            stats = torch.zeros(FLOW_NSTATS, dtype=torch.int64, device=flows.device)
+        rc = self.L.nsd_flow_export_device(self.h, flows.data_ptr(), max_flows, count.data_ptr(), stats.data_ptr(),
+                                           self._stream(stream, flows.device))
+        _check(rc, "nsd_flow_export_device")
+        return flows, count, stats
+
+    def export(self, max_flows=None):
+        """(flows FLOW_DTYPE sorted by `first`, stats u64[8]) in host memory;
+        synchronous."""
+        cap = self.slots if max_flows is None else max_flows
+        flows = np.zeros(max(cap, 1), dtype=FLOW_DTYPE)
+        stats = np.zeros(FLOW_NSTATS, dtype=np.uint64)
+        n = self.L.nsd_flow_export(self.h, flows.ctypes.data, cap, stats.ctypes.data)
+        _check(0 if n >= 0 else n, "nsd_flow_export")
+        return flows[:min(n, cap)], stats
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.nsd_flow_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+
+def flow_batch(frames, desc, mode=PRINT_NORM, linktype=LINKTYPE_EN10MB, max_flows=None):
+    """Host-memory batch through the device (stage, walk, flow update,
+    export): (flows FLOW_DTYPE sorted by `first`, stats u64[8])."""
+    frames = np.ascontiguousarray(frames, dtype=np.uint8)
+    desc = np.ascontiguousarray(desc, dtype=np.uint64)
+    cap = len(desc) if max_flows is None else max_flows
+    flows = np.zeros(max(cap, 1), dtype=FLOW_DTYPE)
+    stats = np.zeros(FLOW_NSTATS, dtype=np.uint64)
+    n = lib().nsd_flow_batch(frames.ctypes.data, frames.nbytes, desc.ctypes.data, len(desc), linktype, mode,
+                             flows.ctypes.data, cap, stats.ctypes.data)
+    _check(0 if n >= 0 else n, "nsd_flow_batch")
+    return flows[:min(n, cap)], stats
+
+
+def flow_cpu(frames, desc, rec, ext=None, base=0, max_flows=None):
+    """The flow aggregation on the host CPU (nsd_flow_cpu) over records
+    already made (REC_DTYPE, ext = the u32 pool their slots index): (flows
+    FLOW_DTYPE sorted by `first`, stats u64[8])."""
+    frames = np.ascontiguousarray(frames, dtype=np.uint8)
+    desc = np.ascontiguousarray(desc, dtype=np.uint64)
+    rec = np.ascontiguousarray(rec, dtype=REC_DTYPE)
+    ext_keep = None if ext is None or len(ext) == 0 else np.ascontiguousarray(ext).view(np.uint32)
+    cap = len(desc) if max_flows is None else max_flows
+    flows = np.zeros(max(cap, 1), dtype=FLOW_DTYPE)
+    stats = np.zeros(FLOW_NSTATS, dtype=np.uint64)
+    n = lib().nsd_flow_cpu(frames.ctypes.data, desc.ctypes.data, len(desc), rec.ctypes.data,
+                           None if ext_keep is None else ext_keep.ctypes.data, base, flows.ctypes.data, cap,
+                           stats.ctypes.data)
+    _check(0 if n >= 0 else n, "nsd_flow_cpu")
+    return flows[:min(n, cap)], stats
+
+
+def pcap_flows(path, table, mode=PRINT_NORM, prog=None):
+    """A capture file's packets into a FlowTable (nsd_pcap_flows): read,
+    optional BpfProgram filter, device walk, flow update; returns the packets
+    fed."""
+    n = lib().nsd_pcap_flows(os.fsencode(path), mode, prog.h if prog is not None else None, table.h)
+    _check(0 if n >= 0 else n, "nsd_pcap_flows")
+    return n
 
 
 # ---- pcap replay front end (nsd_pcap.cpp) ---------------------------------------
