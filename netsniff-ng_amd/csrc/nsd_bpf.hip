@@ -23,7 +23,7 @@
 
 #include <new>
 
-#include "../../include/netsniff_dissect.h"
+#include "nsd_internal.h"
 
 namespace nsdbpf {
 
@@ -379,15 +379,6 @@ struct nsd_bpf_prog {
 	uint32_t *d_verdict = nullptr;
 	size_t n_cap = 0;
 };
-
-static bool hip_ok(hipError_t e, const char *what)
-{
-	if (e != hipSuccess) {
-		fprintf(stderr, "netsniff-dissect bpf: %s: %s\n", what, hipGetErrorString(e));
-		return false;
-	}
-	return true;
-}
 
 // __bpf_validate (bpf.c:388-506), returning 1 / 0 like the reference
 extern "C" int nsd_bpf_validate(const nsd_bpf_insn *prog, uint32_t len)

@@ -14,6 +14,7 @@
 //     and then render the layer's text.
 #include <string.h>
 
+#include "nsd_internal.h"
 #include "nsd_walk.h"
 
 namespace nsd {
@@ -89,9 +90,6 @@ static void walk_packet(const uint8_t *pkt, uint32_t caplen, int start_id, const
 // returns the next ops (0: the chain ends) and the new cursor, the IPv4
 // header checksum and the NSD_F_* flags the layer raised.  The SLL head
 // reads only sll (pkt->sll).
-void cpu_count_packet(const uint8_t *pkt, uint32_t caplen, int linktype, int mode, const nsd_sll_t *sll,
-		      uint64_t *counters);
-
 int cpu_step(int mode, const uint8_t *pkt, uint32_t caplen, int id, uint32_t &data, uint32_t &tail,
 	     uint16_t &ip_csum, uint8_t &flags, const nsd_sll_t *sll)
 {
@@ -122,8 +120,6 @@ int cpu_step(int mode, const uint8_t *pkt, uint32_t caplen, int id, uint32_t &da
 }
 
 } // namespace nsd
-
-__attribute__((visibility("hidden"))) int nsd_start_for(int linktype);   // nsd_host.cpp
 
 // The counters the device adds for one packet, from the host walk, for frames
 // the batch path cannot carry (caplen above NSD_MAX_CAPLEN: the pcap replay

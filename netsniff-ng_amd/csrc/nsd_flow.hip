@@ -37,6 +37,7 @@
 #include <vector>
 
 #include "nsd_flow.h"
+#include "nsd_internal.h"
 
 namespace nsdflow {
 
@@ -301,31 +302,6 @@ __global__ __launch_bounds__(BLOCK) void flow_export(Tab t, uint64_t *out, uint3
 	}
 	if (blockIdx.x == 0 && threadIdx.x < NSD_FLOW_NSTATS)
 		stats_out[threadIdx.x] = t.stats[threadIdx.x];
-}
-
-bool hip_ok(hipError_t e, const char *what)
-{
-	if (e != hipSuccess) {
-		fprintf(stderr, "netsniff-dissect flow: %s: %s\n", what, hipGetErrorString(e));
-		return false;
-	}
-	return true;
-}
-
-template <class T>
-bool grow(T *&p, size_t &cap, size_t need)
-{
-	if (need <= cap)
-		return true;
-	if (p)
-		(void)hipFree(p);
-	p = nullptr;
-	cap = 0;
-	const size_t want = need + need / 4 + 64;
-	if (!hip_ok(hipMalloc(&p, want * sizeof(T)), "hipMalloc"))
-		return false;
-	cap = want;
-	return true;
 }
 
 // device staging of the host-memory entries (nsd_flow_batch, nsd_pcap_flows),

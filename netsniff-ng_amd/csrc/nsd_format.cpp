@@ -22,7 +22,7 @@
 #include <unordered_map>
 #include <vector>
 
-#include "../../include/netsniff_dissect.h"
+#include "nsd_internal.h"
 #include "nsd_lookup.h"
 #include "nsd_ntop.h"
 
@@ -1325,7 +1325,7 @@ std::unordered_map<uint32_t, std::string> g_if_names;
 std::atomic<uint32_t> g_if_gen{ 1 };
 } // namespace
 
-extern "C" __attribute__((visibility("hidden"))) void nsd_if_cache_reset(void)
+extern "C" void nsd_if_cache_reset(void)
 {
 	std::lock_guard<std::mutex> g(g_if_mu);
 	g_if_names.clear();

@@ -14,21 +14,7 @@
 #include <mutex>
 #include <string>
 
-#include "../../include/netsniff_dissect.h"
-
-extern "C" int nsd_launch_dissect_sll(const uint8_t *d_frames, const uint64_t *d_desc, const void *d_sll,
-				      uint32_t n, int start_id, int mode, nsd_rec *d_rec, uint32_t *d_ext,
-				      uint32_t ext_words, uint32_t *d_ext_used, uint64_t *d_counters,
-				      void *d_ws, int grid, hipStream_t stream);
-extern "C" int nsd_launch_dissect(const uint8_t *d_frames, const uint64_t *d_desc, uint32_t n,
-				  int start_id, int mode, nsd_rec *d_rec, uint32_t *d_ext,
-				  uint32_t ext_cap, uint32_t *d_ext_count, uint64_t *d_counters,
-				  void *d_ws, int grid, hipStream_t stream);
-extern "C" int nsd_launch_dissect_rec(const uint8_t *d_frames, const uint64_t *d_desc, const void *d_sll,
-				      uint32_t n, int start_id, int mode, void *d_rec, int compact, uint32_t *d_ext,
-				      uint32_t ext_words, uint32_t *d_ext_used, uint64_t *d_counters, void *d_ws,
-				      int grid, hipStream_t stream);
-extern "C" size_t nsd_launch_workspace_bytes(uint32_t n);
+#include "nsd_internal.h"
 
 // ---- device context ----------------------------------------------------
 namespace {
@@ -49,15 +35,6 @@ struct DevCtx {
 	uint8_t *sll = nullptr; size_t sll_cap = 0;        // per-packet sockaddr_ll (SLL heads)
 };
 DevCtx g_ctx;
-
-bool hip_ok(hipError_t e, const char *what)
-{
-	if (e != hipSuccess) {
-		fprintf(stderr, "netsniff-dissect: %s: %s\n", what, hipGetErrorString(e));
-		return false;
-	}
-	return true;
-}
 
 bool ctx_init(DevCtx &c)
 {
@@ -81,25 +58,10 @@ bool ctx_init(DevCtx &c)
 	return true;
 }
 
-template <class T>
-bool grow(T *&p, size_t &cap, size_t need)
-{
-	if (need <= cap)
-		return true;
-	if (p)
-		(void)hipFree(p);
-	p = nullptr;
-	size_t want = need + need / 4 + 64;
-	if (!hip_ok(hipMalloc(&p, want * sizeof(T)), "hipMalloc"))
-		return false;
-	cap = want;
-	return true;
-}
-
 } // namespace
 
-// linktype -> first ops (dissector.c:75-103); shared with nsd_pipe.cpp
-__attribute__((visibility("hidden"))) int nsd_start_for(int linktype)
+// linktype -> first ops (dissector.c:75-103)
+int nsd_start_for(int linktype)
 {
 	auto is = [&](uint32_t v) { return (uint32_t)linktype == v || (uint32_t)linktype == __builtin_bswap32(v); };
 	if (is(NSD_LINKTYPE_EN10MB)) return NSD_OPS_ETHERNET;
@@ -317,7 +279,7 @@ extern "C" long nsd_tprintf_wrap(const char *in, size_t len, int cols, long *sta
 
 // the device context of the host-memory batch entry (dissector_cleanup_all
 // frees it, nsd_proto.cpp)
-extern "C" __attribute__((visibility("hidden"))) void nsd_device_ctx_release(void)
+extern "C" void nsd_device_ctx_release(void)
 {
 	DevCtx &c = g_ctx;
 	std::lock_guard<std::mutex> lk(c.mu);

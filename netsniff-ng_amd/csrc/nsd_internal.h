@@ -1,0 +1,119 @@
+// nsd_internal.h - everything that crosses a translation unit inside
+// libnsdissect.so and is not part of the ABI (include/netsniff_dissect.h).
+// Every file that defines or uses one of these includes this header, so a
+// declaration that drifts from its definition fails to compile (the
+// extern "C" ones would otherwise link and misbehave).  Each symbol's
+// visibility is settled here: the launchers stay exported (tools call them),
+// NSD_HIDDEN ones are the library's own.
+#ifndef NSD_INTERNAL_H
+#define NSD_INTERNAL_H
+
+#include <hip/hip_runtime_api.h>
+#include <stddef.h>
+#include <stdint.h>
+#include <stdio.h>
+
+#include <string>
+
+#include "../../include/netsniff_dissect.h"
+
+#define NSD_HIDDEN __attribute__((visibility("hidden")))
+
+// ---- HIP helpers of the host code ------------------------------------------
+NSD_HIDDEN inline bool hip_ok(hipError_t e, const char *what)
+{
+	if (e != hipSuccess) {
+		fprintf(stderr, "netsniff-dissect: %s: %s\n", what, hipGetErrorString(e));
+		return false;
+	}
+	return true;
+}
+
+// a device buffer of at least `need` elements (contents not kept); on failure
+// p is NULL and cap 0
+template <class T>
+NSD_HIDDEN inline bool grow(T *&p, size_t &cap, size_t need)
+{
+	if (need <= cap)
+		return true;
+	if (p)
+		(void)hipFree(p);
+	p = nullptr;
+	cap = 0;
+	const size_t want = need + need / 4 + 64;
+	if (!hip_ok(hipMalloc(&p, want * sizeof(T)), "hipMalloc"))
+		return false;
+	cap = want;
+	return true;
+}
+
+// the bytes of the frame buffer a batch's descriptors reach
+inline size_t batch_extent(const nsd_desc_t *desc, size_t n)
+{
+	size_t used = 0;
+	for (size_t j = 0; j < n; j++) {
+		const size_t e = NSD_DESC_OFF(desc[j]) + NSD_DESC_CAPLEN(desc[j]);
+		used = e > used ? e : used;
+	}
+	return used;
+}
+
+// ---- kernel launchers (nsd_kernels.hip) --------------------------------------
+// d_sll: one struct sockaddr_ll (nsd_sll_t, 20 bytes) per packet, or NULL
+// (read as zeros); d_rec: n nsd_rec (16 B), or n nsd_crec (8 B) when `compact`
+extern "C" int nsd_launch_dissect_rec(const uint8_t *d_frames, const uint64_t *d_desc, const void *d_sll,
+				      uint32_t n, int start_id, int mode, void *d_rec, int compact, uint32_t *d_ext,
+				      uint32_t ext_words, uint32_t *d_ext_used, uint64_t *d_counters, void *d_ws,
+				      int grid, hipStream_t stream);
+extern "C" int nsd_launch_dissect(const uint8_t *d_frames, const uint64_t *d_desc, uint32_t n, int start_id,
+				  int mode, nsd_rec *d_rec, uint32_t *d_ext, uint32_t ext_words, uint32_t *d_ext_used,
+				  uint64_t *d_counters, void *d_ws, int grid, hipStream_t stream);
+extern "C" int nsd_launch_dissect_sll(const uint8_t *d_frames, const uint64_t *d_desc, const void *d_sll,
+				      uint32_t n, int start_id, int mode, nsd_rec *d_rec, uint32_t *d_ext,
+				      uint32_t ext_words, uint32_t *d_ext_used, uint64_t *d_counters, void *d_ws,
+				      int grid, hipStream_t stream);
+extern "C" size_t nsd_launch_workspace_bytes(uint32_t n);
+
+// ---- host paths ------------------------------------------------------------
+// linktype -> first ops (nsd_host.cpp)
+NSD_HIDDEN int nsd_start_for(int linktype);
+// a cached pipe for another file: 0, or 1 when it lives on another device
+// than the current one (nsd_pipe.cpp)
+extern "C" NSD_HIDDEN int nsd_pipe_retarget(nsd_pipe *p, int linktype, int mode);
+
+// the flow table's feeds of host batches (nsd_flow.hip)
+extern "C" NSD_HIDDEN long nsd_flow_feed_host(nsd_flow_table *t, const uint8_t *frames, size_t frames_len,
+					      const nsd_desc_t *desc, const nsd_sll_t *sll, uint32_t n, int linktype,
+					      int mode, const nsd_bpf_prog *filter, uint64_t base);
+extern "C" NSD_HIDDEN int nsd_flow_feed_records(nsd_flow_table *t, const uint8_t *frames, size_t frames_len,
+						const nsd_desc_t *desc, uint32_t n, const nsd_rec *rec,
+						const uint32_t *ext, uint32_t ext_words, uint64_t base);
+
+// what dissector_cleanup_all (nsd_proto.cpp) lets go of: the interface name
+// cache (nsd_format.cpp; each replay resets it too), the replay's cached
+// staging (nsd_replay.cpp), the batch entries' device context (nsd_host.cpp)
+extern "C" NSD_HIDDEN void nsd_if_cache_reset(void);
+extern "C" NSD_HIDDEN void nsd_replay_release(void);
+extern "C" NSD_HIDDEN void nsd_device_ctx_release(void);
+
+// ---- host formatter (nsd_format.cpp) and CPU walk (nsd_cpu.hip) -------------
+namespace nsd {
+bool render_layer(std::string &s, const uint8_t *pkt, uint32_t caplen, int id, uint32_t start, uint32_t tail,
+		  int mode, uint16_t ip_csum, bool icmp_bad, const nsd_sll_t *sll, uint32_t &data,
+		  uint32_t &ntail, bool &next);
+void render_hex(std::string &s, const uint8_t *pkt, uint32_t caplen, uint32_t from, uint32_t len);
+void render_ascii(std::string &s, const uint8_t *pkt, uint32_t caplen, uint32_t from, uint32_t len);
+void format_frame_hdr(std::string &s, const nsd_frame_hdr_t &fh, const nsd_sll_t *sll, const uint8_t *pkt,
+		      uint32_t caplen, int linktype, int mode, uint64_t count);
+int render_packet_cpu(std::string &text, const uint8_t *packet, size_t len, int linktype, int mode,
+		      const nsd_sll_t *sll);
+int format_replay_part(std::string &s, const uint8_t *frames, const nsd_desc_t *desc, const nsd_frame_hdr_t *fh,
+		       const nsd_sll_t *sll, const nsd_crec *rec, const uint32_t *ext, uint64_t count0, uint32_t lo,
+		       uint32_t hi, int linktype, int mode);
+int cpu_step(int mode, const uint8_t *pkt, uint32_t caplen, int id, uint32_t &data, uint32_t &tail,
+	     uint16_t &ip_csum, uint8_t &flags, const nsd_sll_t *sll);
+void cpu_count_packet(const uint8_t *pkt, uint32_t caplen, int linktype, int mode, const nsd_sll_t *sll,
+		      uint64_t *counters);
+} // namespace nsd
+
+#endif

@@ -37,6 +37,7 @@
 #include <atomic>
 #include <mutex>
 
+#include "nsd_internal.h"
 #include "nsd_walk.h"
 
 namespace nsd {
@@ -2482,11 +2483,6 @@ extern "C" size_t nsd_launch_workspace_bytes(uint32_t n)
 {
 	return sched_pair_at(n) + 256;
 }
-
-extern "C" int nsd_launch_dissect_rec(const uint8_t *d_frames, const uint64_t *d_desc, const void *d_sll,
-				      uint32_t n, int start_id, int mode, void *d_rec, int compact, uint32_t *d_ext,
-				      uint32_t ext_words, uint32_t *d_ext_used, uint64_t *d_counters, void *d_ws,
-				      int grid, hipStream_t stream);
 
 extern "C" int nsd_launch_dissect(const uint8_t *d_frames, const uint64_t *d_desc, uint32_t n,
 				  int start_id, int mode, nsd_rec *d_rec, uint32_t *d_ext,

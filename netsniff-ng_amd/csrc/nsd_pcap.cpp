@@ -1,8 +1,8 @@
 // nsd_pcap.cpp - the pcap replay front end of the dissector path
 // (`netsniff-ng --in file.pcap`, read_pcap netsniff-ng.c:640-770): a pcap
-// reader that packs records into batches (frames + nsd_desc_t), and a replay
-// driver that feeds them through the optional device BPF filter and the
-// pipelined device walk (nsd_pipe_*) and writes the formatted text.
+// reader that packs records into batches (frames + nsd_desc_t).  Its drivers
+// are in nsd_replay.cpp (the replay, the flow table's file loop), which see
+// it through nsd_pcap_reader.h.
 //
 // Reader semantics follow pcap_io.h and pcap_sg.c:
 //   - file header validation and the *_LL remap for SLL / netlink files
@@ -23,48 +23,21 @@
 //     the batch before it; the batch reader reports NSD_ERR_CAPLEN when it
 //     is the next record, and the replay dissects it through the per-packet
 //     path (nsd_proto.cpp), in file order.
-#include <errno.h>
 #include <fcntl.h>
-#include <pthread.h>
-#include <sched.h>
 #include <stdint.h>
-#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <unistd.h>
 
 #include <sys/mman.h>
 #include <sys/stat.h>
-#include <sys/uio.h>
 
 #include <algorithm>
-#include <atomic>
-#include <chrono>
-#include <condition_variable>
-#include <deque>
-#include <functional>
-#include <mutex>
-#include <string>
-#include <thread>
 #include <vector>
 
-#include "../../include/netsniff_dissect.h"
+#include "nsd_pcap_reader.h"
 
-namespace nsd {
-void format_frame_hdr(std::string &s, const nsd_frame_hdr_t &fh, const nsd_sll_t *sll, const uint8_t *pkt,
-		      uint32_t caplen, int linktype, int mode, uint64_t count);
-int render_packet_cpu(std::string &text, const uint8_t *packet, size_t len, int linktype, int mode,
-		      const nsd_sll_t *sll);
-int format_replay_part(std::string &s, const uint8_t *frames, const nsd_desc_t *desc, const nsd_frame_hdr_t *fh,
-		       const nsd_sll_t *sll, const nsd_crec *rec, const uint32_t *ext, uint64_t count0, uint32_t lo,
-		       uint32_t hi, int linktype, int mode);
-int format_packet_compact(std::string &s, const uint8_t *pkt, uint32_t caplen, int linktype, int mode,
-			  const nsd_crec &rec, uint32_t i, const uint32_t *ext_pool, const nsd_sll_t *sll);
-void cpu_count_packet(const uint8_t *pkt, uint32_t caplen, int linktype, int mode, const nsd_sll_t *sll,
-		      uint64_t *counters);
-}
-
-extern "C" __attribute__((visibility("hidden"))) int nsd_pipe_retarget(nsd_pipe *p, int linktype, int mode);
+using namespace nsd::reader;
 
 namespace {
 
@@ -77,55 +50,10 @@ uint16_t bswap16(uint16_t v) { return __builtin_bswap16(v); }
 
 } // namespace
 
-struct nsd_pcap {
-	int fd = -1;
-	bool swapped = false;
-	uint32_t hdrsize = 16;   // record header bytes (pcap_get_hdr_length)
-	uint32_t ll_extra = 0;   // cooked-header bytes counted in caplen (*_LL)
-	uint32_t linktype = 0;   // as stored in the file header
-	uint32_t magic_raw = 0;  // as stored in the file header
-	uint32_t magic = 0;      // in host order
-	bool nsec = false;
-	bool eof = false;
-	// buffered reader (the scatter-gather reader's iovecs, pcap_sg.c), or a
-	// regular file mapped whole (pcap_mm.c's way; the replay's reader then
-	// only scans the record headers and the pool copies the bodies)
-	std::vector<uint8_t> buf;
-	const uint8_t *map = nullptr;
-	size_t pos = 0, len = 0;
-	// a mapped file's record index, one window at a time (RecIndex below):
-	// the records' header offsets and caplens, ix_i the next one; ix_end =
-	// the walk ended inside the indexed window (no records past the last)
-	std::vector<uint64_t> ix_off;
-	std::vector<uint32_t> ix_cap;
-	size_t ix_i = 0;
-	bool ix_end = false;
-
-	const uint8_t *data() const { return map ? map : buf.data(); }
-	bool fill(size_t need)
-	{
-		if (len - pos >= need)
-			return true;
-		if (map)
-			return false;
-		if (pos) {
-			memmove(buf.data(), buf.data() + pos, len - pos);
-			len -= pos;
-			pos = 0;
-		}
-		if (buf.size() < need)
-			buf.resize(need);
-		while (len < need) {
-			ssize_t r = read(fd, buf.data() + len, buf.size() - len);
-			if (r < 0 && errno == EINTR)
-				continue;
-			if (r <= 0)
-				return false;
-			len += (size_t)r;
-		}
-		return true;
-	}
-};
+bool nsd::reader::has_ll(const nsd_pcap *p)
+{
+	return p->ll_extra != 0 || p->linktype == LT_LINUX_SLL || p->linktype == bswap32(LT_LINUX_SLL);
+}
 
 extern "C" nsd_pcap *nsd_pcap_open(const char *path)
 {
@@ -271,9 +199,6 @@ static void record_meta(const nsd_pcap *p, const uint8_t *h, nsd_sll_t *sll, nsd
 // {pkttype, hatype, len, addr[8], protocol}, every field big-endian in either
 // file byte order): pkttype / hatype / halen from be16, protocol kept as
 // stored (be16), addr copied; family and ifindex stay 0.
-static long read_batch(nsd_pcap *p, uint8_t *frames, size_t cap, nsd_desc_t *desc, nsd_sll_t *sll,
-		       nsd_frame_hdr_t *fh, uint32_t max_n, uint32_t *wire_len, uint64_t *ts_ns, uint8_t *rhdr);
-
 extern "C" long nsd_pcap_read_batch_sll(nsd_pcap *p, uint8_t *frames, size_t cap, nsd_desc_t *desc,
 					nsd_sll_t *sll, uint32_t max_n, uint32_t *wire_len, uint64_t *ts_ns)
 {
@@ -288,8 +213,8 @@ extern "C" long nsd_pcap_read_batch_fh(nsd_pcap *p, uint8_t *frames, size_t cap,
 
 // rhdr (may be NULL): each record's header bytes as stored (hdrsize <= 32,
 // 32-byte stride), for the pcap write-out
-static long read_batch(nsd_pcap *p, uint8_t *frames, size_t cap, nsd_desc_t *desc, nsd_sll_t *sll,
-		       nsd_frame_hdr_t *fh, uint32_t max_n, uint32_t *wire_len, uint64_t *ts_ns, uint8_t *rhdr)
+long nsd::reader::read_batch(nsd_pcap *p, uint8_t *frames, size_t cap, nsd_desc_t *desc, nsd_sll_t *sll,
+			     nsd_frame_hdr_t *fh, uint32_t max_n, uint32_t *wire_len, uint64_t *ts_ns, uint8_t *rhdr)
 {
 	if (!p || !frames || !desc || cap < NSD_FRAME_PAD)
 		return NSD_ERR_ARG;
@@ -356,7 +281,7 @@ static long read_batch(nsd_pcap *p, uint8_t *frames, size_t cap, nsd_desc_t *des
 // batch buffer, src[k] = its header's offset in the file.  fill_range copies
 // a range of the batch afterwards (the replay runs those on its pool).
 // *end = the bytes the batch uses.
-static long scan_batch(nsd_pcap *p, size_t cap, nsd_desc_t *desc, uint64_t *src, uint32_t max_n, size_t *end)
+long nsd::reader::scan_batch(nsd_pcap *p, size_t cap, nsd_desc_t *desc, uint64_t *src, uint32_t max_n, size_t *end)
 {
 	size_t off = 0;
 	uint32_t n = 0;
@@ -406,7 +331,7 @@ static long scan_batch(nsd_pcap *p, size_t cap, nsd_desc_t *desc, uint64_t *src,
 }
 
 // the index window under p->pos is used up (and the walk goes on)
-static bool ix_need(const nsd_pcap *p)
+bool nsd::reader::ix_need(const nsd_pcap *p)
 {
 	size_t i = p->ix_i;
 	while (i < p->ix_off.size() && p->ix_off[i] < p->pos)
@@ -414,8 +339,8 @@ static bool ix_need(const nsd_pcap *p)
 	return i == p->ix_off.size() && !p->ix_end && !p->eof;
 }
 
-static void fill_range(const nsd_pcap *p, uint8_t *frames, const nsd_desc_t *desc, const uint64_t *src,
-		       uint32_t lo, uint32_t hi, nsd_sll_t *sll, nsd_frame_hdr_t *fh, uint8_t *rhdr)
+void nsd::reader::fill_range(const nsd_pcap *p, uint8_t *frames, const nsd_desc_t *desc, const uint64_t *src,
+			     uint32_t lo, uint32_t hi, nsd_sll_t *sll, nsd_frame_hdr_t *fh, uint8_t *rhdr)
 {
 	const uint32_t hs = p->hdrsize;
 	for (uint32_t k = lo; k < hi; k++) {
@@ -440,12 +365,7 @@ static void fill_range(const nsd_pcap *p, uint8_t *frames, const nsd_desc_t *des
 // never met X (a wrong guess that did not fall into step) is walked again
 // from X.  The end rule is read_batch's: a header past the file end, caplen 0
 // or > the 1 MiB replay buffer, or a body past the file end ends the walk.
-struct IxChunk {
-	std::vector<uint64_t> off;
-	std::vector<uint32_t> cap;
-	size_t next = 0;     // where the walk stopped (its last record's end)
-	bool ended = false;  // stopped by the end rule, not at the chunk's end
-};
+// (IxChunk, one chunk's walk: nsd_pcap_reader.h)
 
 // caplen of the header at pos, or 0 when the end rule stops there
 static uint32_t rec_caplen(const nsd_pcap *p, size_t pos)
@@ -512,7 +432,7 @@ static size_t ix_guess(const nsd_pcap *p, size_t lo, size_t hi)
 }
 
 // chunk c of the window [b[0], b[nc]): walked from its guess to b[c + 1]
-static void ix_chunk(const nsd_pcap *p, const std::vector<size_t> &b, int c, IxChunk &out)
+void nsd::reader::ix_chunk(const nsd_pcap *p, const std::vector<size_t> &b, int c, IxChunk &out)
 {
 	out.off.clear();
 	out.cap.clear();
@@ -524,7 +444,7 @@ static void ix_chunk(const nsd_pcap *p, const std::vector<size_t> &b, int c, IxC
 }
 
 // the window's chunk bounds from the exact record start `start`
-static std::vector<size_t> ix_bounds(const nsd_pcap *p, size_t start, size_t window, int nc)
+std::vector<size_t> nsd::reader::ix_bounds(const nsd_pcap *p, size_t start, size_t window, int nc)
 {
 	const size_t end = p->len - start < window ? p->len : start + window;
 	std::vector<size_t> b(nc + 1);
@@ -535,7 +455,7 @@ static std::vector<size_t> ix_bounds(const nsd_pcap *p, size_t start, size_t win
 }
 
 // the exact walk through the chunks' results into p's index
-static void ix_splice(nsd_pcap *p, const std::vector<size_t> &b, std::vector<IxChunk> &ch)
+void nsd::reader::ix_splice(nsd_pcap *p, const std::vector<size_t> &b, std::vector<IxChunk> &ch)
 {
 	const int nc = (int)ch.size();
 	p->ix_off.clear();
@@ -571,21 +491,9 @@ static void ix_splice(nsd_pcap *p, const std::vector<size_t> &b, std::vector<IxC
 		p->ix_end = true;
 }
 
-// the index window from p->pos, chunks run by run(nc, fn) (fn(c) for each
-// chunk c, in any order and on any threads)
-template <class Run>
-static void ix_build(nsd_pcap *p, size_t window, int nc, std::vector<IxChunk> &ch, Run run)
-{
-	const std::vector<size_t> b = ix_bounds(p, p->pos, window, nc);
-	if ((int)ch.size() != nc)
-		ch.resize(nc);
-	run(nc, std::function<void(int)>([&](int c) { ix_chunk(p, b, c, ch[c]); }));
-	ix_splice(p, b, ch);
-}
-
 // the index window (bytes of file per build; NSD_PCAP_IX_WINDOW overrides,
 // for tests)
-static size_t ix_window()
+size_t nsd::reader::ix_window()
 {
 	const char *e = getenv("NSD_PCAP_IX_WINDOW");
 	const long long v = e ? atoll(e) : 0;
@@ -607,15 +515,15 @@ extern "C" long nsd_pcap_index(const char *path, uint64_t window, int chunks, ui
 		nsd_pcap_close(p);
 		return NSD_ERR_ARG;
 	}
-	std::vector<IxChunk> ch;
 	size_t n = 0;
+	const int nc = chunks < 1 ? 1 : chunks;
+	std::vector<IxChunk> ch(nc);
 	while (ix_need(p)) {
+		const std::vector<size_t> b = ix_bounds(p, p->pos, window ? (size_t)window : ix_window(), nc);
 		// (chunks run last to first: the splice does not depend on the order)
-		ix_build(p, window ? (size_t)window : ix_window(), chunks < 1 ? 1 : chunks, ch,
-			 [](int nc, const std::function<void(int)> &fn) {
-				 for (int c = nc - 1; c >= 0; c--)
-					 fn(c);
-			 });
+		for (int c = nc - 1; c >= 0; c--)
+			ix_chunk(p, b, c, ch[c]);
+		ix_splice(p, b, ch);
 		for (size_t i = 0; i < p->ix_off.size(); i++, n++)
 			if (n < max_n) {
 				off[n] = p->ix_off[i];
@@ -633,8 +541,8 @@ extern "C" long nsd_pcap_index(const char *path, uint64_t window, int chunks, ui
 // records a batch cannot carry: its bytes into `frame`, its header as stored
 // into rhdr (may be NULL), its sockaddr_ll / frame header fields into *sll /
 // *fh (record_meta).  Returns caplen, 0 at the end of the replay.
-static long read_one(nsd_pcap *p, std::vector<uint8_t> &frame, nsd_sll_t *sll, nsd_frame_hdr_t *fh,
-		     uint8_t *rhdr)
+long nsd::reader::read_one(nsd_pcap *p, std::vector<uint8_t> &frame, nsd_sll_t *sll, nsd_frame_hdr_t *fh,
+			   uint8_t *rhdr)
 {
 	if (p->eof || !p->fill(p->hdrsize)) {
 		p->eof = true;
@@ -658,911 +566,6 @@ static long read_one(nsd_pcap *p, std::vector<uint8_t> &frame, nsd_sll_t *sll, n
 	record_meta(p, h, sll, fh);
 	p->pos += p->hdrsize + caplen;
 	return caplen;
-}
-
-// The replay loop: read -> [BPF filter on the device] -> device walk (pipelined,
-// `depth` batches in flight) -> host formatter -> [tprintf wrap] -> out_fd.
-// Writes the text dissector_entry_point prints for each accepted record, in
-// file order.  `filter` may be NULL (every record passes, bpf.c:711).
-// `cols` > 0 wraps like tprintf at that width, 0 writes the unwrapped stream.
-// counters (may be NULL) accumulates the per-protocol counter vector.
-// `threads` host threads render each batch (<= 0: up to 16 by the hardware).
-// Returns the records printed, or a negative NSD_ERR_*.
-extern "C" long nsd_replay_pcap(const char *path, int mode, const nsd_bpf_prog *filter, int out_fd,
-				int cols, uint64_t *counters, int threads)
-{
-	return nsd_replay_pcap_out(path, mode, filter, out_fd, cols, counters, threads, -1);
-}
-
-// ---- flows of a capture file (nsd_flow.hip) -----------------------------------
-extern "C" __attribute__((visibility("hidden"))) long nsd_flow_feed_host(nsd_flow_table *t, const uint8_t *frames,
-									  size_t frames_len, const nsd_desc_t *desc,
-									  const nsd_sll_t *sll, uint32_t n, int linktype,
-									  int mode, const nsd_bpf_prog *filter, uint64_t base);
-extern "C" __attribute__((visibility("hidden"))) int nsd_flow_feed_records(nsd_flow_table *t, const uint8_t *frames,
-									    size_t frames_len, const nsd_desc_t *desc,
-									    uint32_t n, const nsd_rec *rec,
-									    const uint32_t *ext, uint32_t ext_words,
-									    uint64_t base);
-
-// read_pcap's loop (netsniff-ng.c:707-756: next record, bpf_run_filter, then
-// the dissector) with the flow table where the dissector's text would be:
-// batches of the reader go through the device filter / walk / update; a
-// record no batch carries is filtered and walked by the per-packet path over
-// its first NSD_MAX_CAPLEN bytes and added with its whole caplen.
-extern "C" long nsd_pcap_flows(const char *path, int mode, const nsd_bpf_prog *filter, nsd_flow_table *t)
-{
-	if (!path || !t || mode < PRINT_NORM || mode > PRINT_NONE)
-		return NSD_ERR_ARG;
-	nsd_pcap *p = nsd_pcap_open(path);
-	if (!p)
-		return NSD_ERR_ARG;
-	const int lt = (int)p->linktype;
-	const bool has_ll = p->ll_extra != 0 || p->linktype == LT_LINUX_SLL || p->linktype == bswap32(LT_LINUX_SLL);
-	constexpr size_t CAP = 16u << 20;
-	constexpr uint32_t MAX_N = 1u << 16;
-	std::vector<uint8_t> frames(CAP), big;
-	std::vector<nsd_desc_t> desc(MAX_N);
-	std::vector<nsd_sll_t> sll(MAX_N);
-	uint64_t fed = 0;
-	long rc = NSD_OK;
-	while (rc == NSD_OK) {
-		const long n = read_batch(p, frames.data(), CAP, desc.data(), sll.data(), nullptr, MAX_N, nullptr, nullptr,
-					  nullptr);
-		if (n == 0)
-			break;
-		if (n > 0) {
-			size_t used = 0;
-			for (long j = 0; j < n; j++) {
-				const size_t e = NSD_DESC_OFF(desc[j]) + NSD_DESC_CAPLEN(desc[j]);
-				used = e > used ? e : used;
-			}
-			const long k = nsd_flow_feed_host(t, frames.data(), used, desc.data(), has_ll ? sll.data() : nullptr,
-							  (uint32_t)n, lt, mode, filter, fed);
-			if (k < 0)
-				rc = k;
-			else
-				fed += (uint64_t)k;
-			continue;
-		}
-		if (n != NSD_ERR_CAPLEN) {
-			rc = n;
-			break;
-		}
-		nsd_sll_t ll;
-		const long caplen = read_one(p, big, &ll, nullptr, nullptr);
-		if (caplen <= 0)
-			break;
-		const nsd_desc_t d = NSD_DESC(0, caplen);
-		if (filter) {
-			uint32_t v = 0;
-			rc = nsd_bpf_filter_batch(filter, big.data(), (size_t)caplen, &d, 1, &v);
-			if (rc != NSD_OK || !v)
-				continue;
-		}
-		const uint32_t head = (uint32_t)caplen < NSD_MAX_CAPLEN ? (uint32_t)caplen : NSD_MAX_CAPLEN;
-		nsd_rec rec;
-		uint32_t ext[NSD_EXT_WORDS(NSD_EXT_MAX_LAYERS)] = { 0 };
-		rc = nsd_walk_packet_cpu(big.data(), head, lt, mode, has_ll ? &ll : nullptr, &rec, ext,
-					 NSD_EXT_WORDS(NSD_EXT_MAX_LAYERS), nullptr);
-		if (rc == NSD_OK)
-			rc = nsd_flow_feed_records(t, big.data(), head, &d, 1, &rec, ext, NSD_EXT_WORDS(NSD_EXT_MAX_LAYERS), fed);
-		if (rc == NSD_OK)
-			fed++;
-	}
-	nsd_pcap_close(p);
-	return rc == NSD_OK ? (long)fed : rc;
-}
-
-static bool write_all(int fd, const void *buf, size_t n)
-{
-	const uint8_t *w = (const uint8_t *)buf;
-	while (n) {
-		ssize_t r = write(fd, w, n);
-		if (r < 0 && errno == EINTR)
-			continue;
-		if (r <= 0)
-			return false;
-		w += r;
-		n -= (size_t)r;
-	}
-	return true;
-}
-
-// pcap_generic_push_fhdr -> pcap_prepare_header (pcap_io.h:813-843, 936-950)
-// with the replayed file's magic and link type as read_pcap holds them
-// (ctx->magic / ctx->link_type, netsniff-ng.c:694-695): the *_LL remap undone
-// (the stored magic), version 2.4, thiszone 0, sigfigs 0, snaplen 65535,
-// link type swapped once more when the magic is a swapped one (as the
-// reference does with the as-stored value).  A swapped SLL / netlink file
-// holds the remapped magic swab32(*_MAGIC_LL), which pcap_magic_is_swapped
-// does not recognise (pcap_io.h:307-320): its header is written unswapped,
-// the link type as stored.
-static bool push_fhdr(const nsd_pcap *p, int fd)
-{
-	uint8_t h[24];
-	const bool sw = p->swapped && p->ll_extra == 0;
-	const uint16_t vmaj = sw ? bswap16(2) : 2, vmin = sw ? bswap16(4) : 4;
-	const uint32_t zero = 0, snap = sw ? bswap32(65535) : 65535;
-	const uint32_t lt = sw ? bswap32(p->linktype) : p->linktype;
-	memcpy(h, &p->magic_raw, 4);
-	memcpy(h + 4, &vmaj, 2);
-	memcpy(h + 6, &vmin, 2);
-	memcpy(h + 8, &zero, 4);
-	memcpy(h + 12, &zero, 4);
-	memcpy(h + 16, &snap, 4);
-	memcpy(h + 20, &lt, 4);
-	return write_all(fd, h, sizeof(h));
-}
-
-// The replay's staging: pinned host buffers per batch slot and the device pipe.
-namespace {
-constexpr uint32_t BATCH = 1u << 16;
-constexpr size_t FRAME_BYTES = 32ull << 20;
-constexpr int DEPTH = 3;           // batches on the device
-constexpr int NSLOT = DEPTH + 4;   // + being copied, being rendered, rendered, being written
-// the side words and room for a quarter of a batch to take a deep (> 12
-// layer) entry; a chain the pool cannot hold is rendered per packet
-constexpr uint32_t EXT_WORDS = BATCH + BATCH / 4 * NSD_EXT_WORDS(NSD_EXT_MAX_LAYERS);
-
-// one formatter part's text: a cache line of its own, as every append writes
-// the string's length (adjacent std::strings shared lines between the pool's
-// threads: per-packet false sharing that cost the 16-thread pool 3x per record)
-struct alignas(64) TextPart {
-	std::string s;
-};
-
-struct ReplayRes {
-	nsd_pipe *pipe = nullptr;
-	struct {
-		uint8_t *frames;
-		nsd_desc_t *desc;
-		nsd_sll_t *sll;
-		nsd_crec *rec;
-		uint32_t *ext;
-	} buf[NSLOT] = {};
-	// each record's frame header fields (show_frame_hdr)
-	std::vector<nsd_frame_hdr_t> fh[NSLOT];
-	// a mapped file's record offsets (scan_batch)
-	std::vector<uint64_t> src[NSLOT];
-	// the formatter parts' text buffers per slot, kept with their capacity:
-	// regrown per replay they faulted in hundreds of MB of fresh pages,
-	// with the formatter threads queued on the page-table lock
-	std::vector<TextPart> part[NSLOT];
-	bool ready() const { return pipe != nullptr; }
-	long create(int lt, int mode)
-	{
-		pipe = nsd_pipe_create_compact(BATCH, FRAME_BYTES, EXT_WORDS, DEPTH, lt, mode);
-		if (!pipe)
-			return NSD_ERR_HIP;
-		for (auto &x : buf) {
-			x.frames = (uint8_t *)nsd_host_alloc(FRAME_BYTES);
-			x.desc = (nsd_desc_t *)nsd_host_alloc(BATCH * sizeof(nsd_desc_t));
-			x.sll = (nsd_sll_t *)nsd_host_alloc(BATCH * sizeof(nsd_sll_t));
-			x.rec = (nsd_crec *)nsd_host_alloc(BATCH * sizeof(nsd_crec));
-			x.ext = (uint32_t *)nsd_host_alloc(EXT_WORDS * sizeof(uint32_t));
-			if (!x.frames || !x.desc || !x.sll || !x.rec || !x.ext) {
-				release();
-				return NSD_ERR_NOMEM;
-			}
-		}
-		for (auto &v : fh)
-			v.resize(BATCH);
-		for (auto &v : src)
-			v.resize(BATCH);
-		return NSD_OK;
-	}
-	void release()
-	{
-		for (auto &x : buf) {
-			nsd_host_free(x.frames);
-			nsd_host_free(x.desc);
-			nsd_host_free(x.sll);
-			nsd_host_free(x.rec);
-			nsd_host_free(x.ext);
-			x = {};
-		}
-		for (auto &v : part)
-			std::vector<TextPart>().swap(v);
-		for (auto &v : fh)
-			std::vector<nsd_frame_hdr_t>().swap(v);
-		for (auto &v : src)
-			std::vector<uint64_t>().swap(v);
-		nsd_pipe_destroy(pipe);
-		pipe = nullptr;
-	}
-};
-std::mutex g_replay_mu;
-ReplayRes g_replay;
-
-// The CPUs the formatter pool runs on: one per physical core (an SMT
-// sibling formats at a fraction of a core's rate), those of the calling
-// thread's NUMA node first, of the CPUs this process may use.  Empty when
-// the topology cannot be read (then nothing is pinned), or NSD_REPLAY_PIN=0.
-// The topology is read from /sys once per process.
-struct CpuTopo {
-	int cpu;
-	long pkg, core;
-	int node;
-};
-const std::vector<CpuTopo> &cpu_topology()
-{
-	static const std::vector<CpuTopo> topo = [] {
-		std::vector<CpuTopo> t;
-		auto rd = [](int cpu, const char *what) -> long {
-			char path[128];
-			snprintf(path, sizeof(path), "/sys/devices/system/cpu/cpu%d/%s", cpu, what);
-			FILE *f = fopen(path, "r");
-			if (!f)
-				return -1;
-			long v = -1;
-			if (fscanf(f, "%ld", &v) != 1)
-				v = -1;
-			fclose(f);
-			return v;
-		};
-		for (int c = 0; c < CPU_SETSIZE; c++) {
-			const long pkg = rd(c, "topology/physical_package_id"), core = rd(c, "topology/core_id");
-			if (pkg < 0 || core < 0)
-				continue;
-			int node = 0;
-			for (int n = 0; n < 64; n++) {
-				char path[128];
-				snprintf(path, sizeof(path), "/sys/devices/system/cpu/cpu%d/node%d", c, n);
-				if (access(path, F_OK) == 0) {
-					node = n;
-					break;
-				}
-			}
-			t.push_back({ c, pkg, core, node });
-		}
-		return t;
-	}();
-	return topo;
-}
-
-std::vector<int> pool_cpus()
-{
-	std::vector<int> out;
-	const char *e = getenv("NSD_REPLAY_PIN");
-	if (e && e[0] == '0')
-		return out;
-	cpu_set_t set;
-	if (sched_getaffinity(0, sizeof(set), &set) != 0)
-		return out;
-	const std::vector<CpuTopo> &topo = cpu_topology();
-	const int me = sched_getcpu();
-	const CpuTopo *mine = nullptr;
-	for (const CpuTopo &t : topo)
-		if (t.cpu == me)
-			mine = &t;
-	std::vector<std::pair<long, long>> seen;   // (package, core)
-	std::vector<int> near, far;
-	int first = -1;                            // the caller's core
-	for (const CpuTopo &t : topo) {
-		if (!CPU_ISSET(t.cpu, &set))
-			continue;
-		bool dup = false;
-		for (auto &x : seen)
-			dup = dup || (x.first == t.pkg && x.second == t.core);
-		if (dup)
-			continue;
-		seen.emplace_back(t.pkg, t.core);
-		if (mine && t.pkg == mine->pkg && t.core == mine->core)
-			first = t.cpu;
-		else
-			(!mine || t.node == mine->node ? near : far).push_back(t.cpu);
-	}
-	// the caller's core first (the pool leaves it to the reader)
-	if (first >= 0)
-		out.push_back(first);
-	out.insert(out.end(), near.begin(), near.end());
-	out.insert(out.end(), far.begin(), far.end());
-	return out;
-}
-
-// Stage times of one replay, printed to stderr when NSD_REPLAY_STATS is set
-// in the environment (the pipeline's balance on a given host): the reader,
-// the device waits, the formatter jobs (summed over the pool), the writer,
-// and the reader's waits for a free slot.
-struct ReplayStats {
-	std::atomic<uint64_t> read{ 0 }, scan{ 0 }, ix{ 0 }, dev{ 0 }, fmt{ 0 }, write{ 0 }, slot{ 0 }, jobs{ 0 };
-	static uint64_t now()
-	{
-		return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(
-			       std::chrono::steady_clock::now().time_since_epoch())
-			.count();
-	}
-};
-} // namespace
-
-// As nsd_replay_pcap; with pcap_fd >= 0 also the `--out f.pcap` write-out
-// of read_pcap (netsniff-ng.c:636, 693-697, 739-746): the file header, then
-// every record that passed the filter exactly as it was read (record header
-// incl. the *_LL cooked header, then its bytes: write_pcap(fdo, &phdr, magic,
-// out, pcap_get_length) of pcap_sg.c / pcap_rw.c), in file order.
-//
-// Three stages run at once over a ring of batch slots (pinned host buffers):
-//   - this thread reads a batch, filters it and submits it to the device
-//     pipe (compact records, DEPTH batches in flight); when the pipe is full
-//     it completes the oldest batch and queues its render jobs;
-//   - `threads` formatter threads (a pool for the whole replay) render the
-//     batch's contiguous packet ranges, each into its own text buffer;
-//   - a writer thread writes each batch's buffers in file order (writev, or
-//     through the tprintf wrap when cols > 0), then the pcap write-out, and
-//     frees the slot.
-// So reading and walking batch k+1 overlap the rendering of batch k and the
-// writing of batch k-1.  A record above NSD_MAX_CAPLEN waits for everything
-// before it to be written, then goes through the per-packet path.
-extern "C" __attribute__((visibility("hidden"))) void nsd_if_cache_reset(void);   // nsd_format.cpp
-
-extern "C" long nsd_replay_pcap_out(const char *path, int mode, const nsd_bpf_prog *filter, int out_fd,
-				    int cols, uint64_t *counters, int threads, int pcap_fd)
-{
-	if (threads <= 0) {
-		const unsigned hc = std::thread::hardware_concurrency();
-		threads = hc ? (int)(hc < 16 ? hc : 16) : 1;
-	}
-	if (threads > 64)
-		threads = 64;
-	nsd_pcap *p = nsd_pcap_open(path);
-	if (!p)
-		return NSD_ERR_ARG;
-	nsd_if_cache_reset();   // interface names as they are now (renames since an earlier replay)
-	const int lt = (int)p->linktype;
-	// the dissector's SLL head reads the sockaddr_ll: an *_LL file's cooked
-	// headers, or a Kuznetzov / Borkmann file of an SLL link type (the frame
-	// headers read it for every file)
-	const bool has_ll = p->ll_extra != 0 || p->linktype == LT_LINUX_SLL || p->linktype == bswap32(LT_LINUX_SLL);
-	if (pcap_fd >= 0 && !push_fhdr(p, pcap_fd)) {
-		nsd_pcap_close(p);
-		return NSD_ERR_ARG;
-	}
-	// the pinned staging and the device pipe (hundreds of MB: their set-up
-	// costs about as much as replaying a million records) are kept for the
-	// process and reused by the next replay; a replay running beside another
-	// gets its own
-	std::unique_lock<std::mutex> cache_lk(g_replay_mu, std::try_to_lock);
-	ReplayRes own;
-	ReplayRes &res = cache_lk.owns_lock() ? g_replay : own;
-	long rc = res.ready() ? (long)nsd_pipe_retarget(res.pipe, lt, mode) : (long)res.create(lt, mode);
-	if (rc == 1) {
-		// the cached set was made on another device than the current one
-		res.release();
-		rc = res.create(lt, mode);
-	}
-	if (rc != NSD_OK) {
-		nsd_pcap_close(p);
-		return rc;
-	}
-	nsd_pipe *const pipe = res.pipe;
-	struct Slot {
-		uint8_t *frames = nullptr;
-		nsd_desc_t *desc = nullptr;
-		nsd_sll_t *sll = nullptr;
-		uint8_t *rhdr = nullptr;   // record headers as read (pcap write-out)
-		nsd_frame_hdr_t *fh = nullptr;
-		uint64_t *src = nullptr;   // record offsets in a mapped file
-		int fill_left = 0;         // copy jobs of the batch not done
-		uint64_t count0 = 0;       // the packet counter of the batch's first record
-		nsd_crec *rec = nullptr;
-		uint32_t *ext = nullptr;
-		uint32_t *verdict = nullptr;
-		uint32_t ext_used = 0, n = 0;
-		uint64_t cnt[NSD_NCOUNTERS];
-		int status = 0;
-		uint64_t seq = 0;
-		int parts = 0, left = 0;   // render jobs, jobs not done
-		std::vector<TextPart> *part = nullptr;   // res.part[slot]
-		long prc = NSD_OK;         // first render error
-	};
-	std::vector<Slot> b(NSLOT);
-	std::vector<uint32_t> verdicts(filter ? (size_t)NSLOT * BATCH : 0);
-	std::vector<uint8_t> rhdrs(pcap_fd >= 0 ? (size_t)NSLOT * BATCH * 32 : 0);
-	for (int k = 0; k < NSLOT; k++) {
-		Slot &x = b[k];
-		x.frames = res.buf[k].frames;
-		x.desc = res.buf[k].desc;
-		x.rec = res.buf[k].rec;
-		x.ext = res.buf[k].ext;
-		x.sll = res.buf[k].sll;
-		x.fh = res.fh[k].data();
-		x.src = res.src[k].data();
-		x.verdict = filter ? &verdicts[(size_t)k * BATCH] : nullptr;
-		x.rhdr = pcap_fd >= 0 ? &rhdrs[(size_t)k * BATCH * 32] : nullptr;
-		x.part = &res.part[k];
-		if (x.part->size() < (size_t)threads)
-			x.part->resize(threads);
-	}
-
-	std::mutex mu;
-	std::condition_variable cv_job, cv_write, cv_free, cv_fill;
-	ReplayStats st;
-	const bool stats = getenv("NSD_REPLAY_STATS") != nullptr;
-	const uint64_t t_start = ReplayStats::now();
-	// (slot, part, parts): render jobs, and the jobs of a mapped file's
-	// reader (copies of a batch, parts > 0; record index chunks, slot -1),
-	// which the pool takes first, in the order given
-	struct Job {
-		int slot, part, parts;
-	};
-	std::deque<Job> jobs, fills;
-	std::vector<int> free_slots;
-	for (int k = NSLOT - 1; k >= 0; k--)
-		free_slots.push_back(k);
-	std::deque<int> to_write;               // slots in file order, waiting for their render
-	uint64_t next_seq = 0, written = 0;     // batches handed to the writer / written
-	long err = rc;                          // first error of any stage
-	bool stop = false;
-	long printed = 0;
-	uint64_t counted = 0;                   // read_pcap's ctx->tx_packets (netsniff-ng.c:730)
-	long wrap_state = 0;
-	std::string wrapped;
-
-	// the writer's output of one piece of text (wrapped when cols > 0)
-	auto put_text = [&](const std::string &t) -> long {
-		if (cols > 0 && !t.empty()) {
-			wrapped.resize(2 * t.size() + 16);
-			const long k = nsd_tprintf_wrap(t.data(), t.size(), cols, &wrap_state, &wrapped[0], wrapped.size());
-			if (k < 0)
-				return k;
-			return write_all(out_fd, wrapped.data(), (size_t)k) ? NSD_OK : NSD_ERR_ARG;
-		}
-		return write_all(out_fd, t.data(), t.size()) ? NSD_OK : NSD_ERR_ARG;
-	};
-	auto put_parts = [&](const Slot &x) -> long {
-		if (cols > 0) {
-			for (int t = 0; t < x.parts; t++) {
-				const long r = put_text((*x.part)[t].s);
-				if (r != NSD_OK)
-					return r;
-			}
-			return NSD_OK;
-		}
-		std::vector<struct iovec> iov;
-		for (int t = 0; t < x.parts; t++)
-			if (!(*x.part)[t].s.empty())
-				iov.push_back({ (void *)(*x.part)[t].s.data(), (*x.part)[t].s.size() });
-		size_t k = 0;
-		while (k < iov.size()) {
-			const int cnt = (int)(iov.size() - k < 512 ? iov.size() - k : 512);
-			ssize_t w = writev(out_fd, &iov[k], cnt);
-			if (w < 0 && errno == EINTR)
-				continue;
-			if (w <= 0)
-				return NSD_ERR_ARG;
-			while (w > 0 && k < iov.size()) {   // advance past what was written
-				if ((size_t)w >= iov[k].iov_len) {
-					w -= (ssize_t)iov[k].iov_len;
-					k++;
-				} else {
-					iov[k].iov_base = (uint8_t *)iov[k].iov_base + w;
-					iov[k].iov_len -= (size_t)w;
-					w = 0;
-				}
-			}
-		}
-		return NSD_OK;
-	};
-	auto put_records = [&](const Slot &x) -> long {
-		if (pcap_fd < 0)
-			return NSD_OK;
-		std::string recs;
-		for (uint32_t k = 0; k < x.n; k++) {
-			recs.append((const char *)x.rhdr + 32 * (size_t)k, p->hdrsize);
-			recs.append((const char *)x.frames + NSD_DESC_OFF(x.desc[k]), NSD_DESC_CAPLEN(x.desc[k]));
-		}
-		return write_all(pcap_fd, recs.data(), recs.size()) ? NSD_OK : NSD_ERR_ARG;
-	};
-
-	// formatter pool: part t of a slot = its packets [n t / parts, n (t+1) / parts)
-	auto render = [&](Slot &x, int t) -> long {
-		const uint32_t lo = (uint32_t)((uint64_t)x.n * t / x.parts), hi = (uint32_t)((uint64_t)x.n * (t + 1) / x.parts);
-		std::string &s = (*x.part)[t].s;
-		s.clear();
-		return nsd::format_replay_part(s, x.frames, x.desc, x.fh, x.sll, x.rec, x.ext, x.count0, lo, hi, lt, mode);
-	};
-	// copy job `q` of `parts` of a mapped file's batch
-	auto fill_part = [&](Slot &x, int q, int parts) {
-		const uint32_t lo = (uint32_t)((uint64_t)x.n * q / parts), hi = (uint32_t)((uint64_t)x.n * (q + 1) / parts);
-		fill_range(p, x.frames, x.desc, x.src, lo, hi, x.sll, x.fh, x.rhdr);
-	};
-	// the copy of a scanned batch (x.n records in slot k) goes to the pool
-	// while the reader scans the next batch; wait_fill joins it (the reader
-	// takes the batch's parts still queued)
-	auto start_fill = [&](Slot &x, int k) {
-		const int parts = x.n < 4096 ? 1 : (int)std::min<uint32_t>((uint32_t)threads + 1, x.n / 2048);
-		std::lock_guard<std::mutex> g(mu);
-		x.fill_left = parts;
-		for (int q = 0; q < parts; q++)
-			fills.push_back({ k, q, parts });
-		cv_job.notify_all();
-	};
-	// the record index's chunk jobs (slot -1) of the window being built
-	std::function<void(int)> ix_fn;
-	int ix_left = 0;
-	std::vector<IxChunk> ix_chunks;
-	// the front copy job, taken with mu held (returns with it held)
-	auto run_fill = [&](std::unique_lock<std::mutex> &lk) {
-		const Job j = fills.front();
-		fills.pop_front();
-		lk.unlock();
-		if (j.slot < 0)
-			ix_fn(j.part);
-		else
-			fill_part(b[j.slot], j.part, j.parts);
-		lk.lock();
-		if (j.slot < 0 ? --ix_left == 0 : --b[j.slot].fill_left == 0)
-			cv_fill.notify_all();
-	};
-	auto wait_fill = [&](Slot &x) {
-		std::unique_lock<std::mutex> lk(mu);
-		while (x.fill_left > 0) {
-			if (!fills.empty())
-				run_fill(lk);   // (in file order: this batch's or an earlier one's)
-			else
-				cv_fill.wait(lk);
-		}
-	};
-	// a mapped file's index windows: the chunks of the window after the one
-	// the reader scans run on the pool meanwhile (a window's start is the end
-	// of the one before, known once that one is spliced)
-	std::vector<size_t> ix_b;
-	bool ix_flight = false;
-	auto ix_launch = [&](size_t start) {
-		const int nc = threads + 1;
-		ix_b = ix_bounds(p, start, ix_window(), nc);
-		if ((int)ix_chunks.size() != nc)
-			ix_chunks.resize(nc);
-		std::lock_guard<std::mutex> g(mu);
-		ix_fn = [&](int c) { ix_chunk(p, ix_b, c, ix_chunks[c]); };
-		ix_left = nc;
-		for (int c = 0; c < nc; c++)
-			fills.push_back({ -1, c, nc });
-		ix_flight = true;
-		cv_job.notify_all();
-	};
-	auto ix_join = [&]() {
-		std::unique_lock<std::mutex> lk(mu);
-		while (ix_left > 0) {
-			if (!fills.empty())
-				run_fill(lk);
-			else
-				cv_fill.wait(lk);
-		}
-		ix_flight = false;
-	};
-	auto build_index = [&]() {
-		if (!ix_flight)
-			ix_launch(p->pos);
-		ix_join();
-		ix_splice(p, ix_b, ix_chunks);
-		if (!p->ix_end)
-			ix_launch(p->ix_off.empty() ? ix_b[0] : p->ix_off.back() + p->hdrsize + p->ix_cap.back());
-	};
-	std::vector<std::thread> pool;
-	const std::vector<int> cpus = pool_cpus();
-	for (int t = 0; t < threads; t++)
-		pool.emplace_back([&, t]() {
-			if (!cpus.empty()) {
-				// one formatter per physical core, near the caller; the
-				// caller's own core (the reader) is left out while others remain
-				cpu_set_t one;
-				CPU_ZERO(&one);
-				const size_t k = cpus.size() > 1 ? 1 + (size_t)t % (cpus.size() - 1) : 0;
-				CPU_SET(cpus[k], &one);
-				(void)pthread_setaffinity_np(pthread_self(), sizeof(one), &one);
-			}
-			std::unique_lock<std::mutex> lk(mu);
-			for (;;) {
-				cv_job.wait(lk, [&] { return stop || !jobs.empty() || !fills.empty(); });
-				if (jobs.empty() && fills.empty())
-					return;
-				if (!fills.empty()) {
-					run_fill(lk);
-					continue;
-				}
-				const Job j = jobs.front();
-				jobs.pop_front();
-				lk.unlock();
-				const uint64_t t0 = stats ? ReplayStats::now() : 0;
-				const long r = render(b[j.slot], j.part);
-				if (stats) {
-					st.fmt += ReplayStats::now() - t0;
-					st.jobs++;
-				}
-				lk.lock();
-				Slot &x = b[j.slot];
-				if (r != NSD_OK && x.prc == NSD_OK)
-					x.prc = r;
-				if (--x.left == 0)
-					cv_write.notify_all();
-			}
-		});
-	std::thread writer([&]() {
-		std::unique_lock<std::mutex> lk(mu);
-		for (;;) {
-			cv_write.wait(lk, [&] { return (!to_write.empty() && b[to_write.front()].left == 0) ||
-						       (stop && to_write.empty()); });
-			if (to_write.empty())
-				return;
-			const int k = to_write.front();
-			to_write.pop_front();
-			Slot &x = b[k];
-			long r = x.prc;
-			const bool skip = err != NSD_OK;
-			lk.unlock();
-			const uint64_t t0 = stats ? ReplayStats::now() : 0;
-			if (!skip && r == NSD_OK)
-				r = put_parts(x);
-			if (!skip && r == NSD_OK)
-				r = put_records(x);
-			if (stats)
-				st.write += ReplayStats::now() - t0;
-			lk.lock();
-			if (r != NSD_OK && err == NSD_OK)
-				err = r;
-			if (!skip && r == NSD_OK)
-				printed += x.n;
-			written++;
-			free_slots.push_back(k);
-			cv_free.notify_all();
-		}
-	});
-
-	// the device batch in slot k completed: queue its render jobs
-	std::deque<int> on_device;
-	auto complete_oldest = [&]() -> long {
-		const int k = on_device.front();
-		on_device.pop_front();
-		Slot &x = b[k];
-		const uint64_t t0 = stats ? ReplayStats::now() : 0;
-		const int ws = nsd_pipe_wait(pipe);
-		if (stats)
-			st.dev += ReplayStats::now() - t0;
-		long r = ws != NSD_OK ? (ws < 0 ? ws : NSD_ERR_HIP) : x.status;
-		if (r == NSD_OK && counters)
-			for (int c = 0; c < NSD_NCOUNTERS; c++)
-				counters[c] += x.cnt[c];
-		std::lock_guard<std::mutex> g(mu);
-		x.parts = x.n < 2048 ? 1 : threads;
-		x.left = x.parts;
-		x.prc = r;
-		x.seq = next_seq++;
-		to_write.push_back(k);
-		if (r == NSD_OK) {
-			for (int t = 0; t < x.parts; t++)
-				jobs.push_back({ k, t, 0 });
-			cv_job.notify_all();
-		} else {
-			x.left = 0;
-			cv_write.notify_all();
-		}
-		return r;
-	};
-	// everything read so far through the device, rendered and written
-	auto flush_all = [&]() -> long {
-		while (!on_device.empty())
-			complete_oldest();
-		std::unique_lock<std::mutex> lk(mu);
-		cv_free.wait(lk, [&] { return written == next_seq; });
-		return err;
-	};
-	// a record longer than a batch can carry: after the batches before it,
-	// filtered and dissected on its own through the per-packet path
-	std::vector<uint8_t> big;
-	auto one_big = [&]() -> long {
-		long r = flush_all();
-		if (r != NSD_OK)
-			return r;
-		nsd_sll_t ll;
-		nsd_frame_hdr_t fh;
-		uint8_t hdr[32];
-		const long caplen = read_one(p, big, &ll, &fh, hdr);
-		if (caplen <= 0)
-			return NSD_OK;
-		if (filter) {
-			const nsd_desc_t d = NSD_DESC(0, caplen);
-			uint32_t v = 0;
-			r = nsd_bpf_filter_batch(filter, big.data(), (size_t)caplen, &d, 1, &v);
-			if (r != NSD_OK)
-				return r;
-			if (!v)
-				return NSD_OK;
-		}
-		if (counters)
-			nsd::cpu_count_packet(big.data(), (uint32_t)caplen, lt, mode, has_ll ? &ll : nullptr, counters);
-		std::string text;
-		nsd::format_frame_hdr(text, fh, &ll, big.data(), (uint32_t)caplen, lt, mode, ++counted);
-		r = nsd::render_packet_cpu(text, big.data(), (size_t)caplen, lt, mode, &ll);
-		if (r != NSD_OK)
-			return r;
-		// (the writer is idle: every batch before this record is written)
-		r = put_text(text);
-		if (r == NSD_OK && pcap_fd >= 0 &&
-		    !(write_all(pcap_fd, hdr, p->hdrsize) && write_all(pcap_fd, big.data(), (size_t)caplen)))
-			r = NSD_ERR_ARG;
-		if (r == NSD_OK)
-			printed++;
-		return r;
-	};
-
-	// slot k's n records read: filtered (bpf_run_filter per record before the
-	// dissector, netsniff-ng.c:723-725) and submitted to the device
-	auto give_back = [&](int slot) {
-		std::lock_guard<std::mutex> g(mu);
-		free_slots.push_back(slot);
-	};
-	auto submit_slot = [&](int k, long n) -> long {
-		Slot &x = b[k];
-		size_t used = 0;
-		for (long j = 0; j < n; j++) {
-			const size_t e = NSD_DESC_OFF(x.desc[j]) + NSD_DESC_CAPLEN(x.desc[j]);
-			used = e > used ? e : used;
-		}
-		if (filter) {
-			// bpf_run_filter per record before the dissector (netsniff-ng.c:723-725)
-			int r = nsd_bpf_filter_batch(filter, x.frames, used, x.desc, (uint32_t)n, x.verdict);
-			if (r != NSD_OK) {
-				give_back(k);
-				return r;
-			}
-			long m = 0;
-			for (long j = 0; j < n; j++)
-				if (x.verdict[j]) {
-					x.sll[m] = x.sll[j];
-					x.fh[m] = x.fh[j];
-					if (x.rhdr && m != j)
-						memcpy(x.rhdr + 32 * (size_t)m, x.rhdr + 32 * (size_t)j, 32);
-					x.desc[m++] = x.desc[j];
-				}
-			n = m;
-			if (n == 0) {
-				give_back(k);
-				return NSD_OK;
-			}
-		}
-		if ((int)on_device.size() == DEPTH)
-			complete_oldest();
-		x.n = (uint32_t)n;
-		x.count0 = counted + 1;
-		counted += x.n;
-		x.status = NSD_OK;
-		memset(x.cnt, 0, sizeof(x.cnt));
-		int r = nsd_pipe_submit_compact(pipe, x.frames, used, x.desc, has_ll ? x.sll : nullptr, x.n, x.rec, x.ext,
-						&x.ext_used, x.cnt, &x.status);
-		if (r != NSD_OK) {
-			give_back(k);
-			return r;
-		}
-		on_device.push_back(k);
-		return NSD_OK;
-	};
-	int pend = -1;     // a mapped file's batch whose copy is on the pool
-	long pend_n = 0;
-	while (rc == NSD_OK) {
-		int k;
-		{
-			std::unique_lock<std::mutex> lk(mu);
-			if (err != NSD_OK) {
-				rc = err;
-				break;
-			}
-			if (free_slots.empty()) {
-				lk.unlock();
-				if (!on_device.empty()) {
-					complete_oldest();
-					continue;
-				}
-				lk.lock();
-				const uint64_t t0 = stats ? ReplayStats::now() : 0;
-				cv_free.wait(lk, [&] { return !free_slots.empty(); });
-				if (stats)
-					st.slot += ReplayStats::now() - t0;
-			}
-			k = free_slots.back();
-			free_slots.pop_back();
-		}
-		Slot &x = b[k];
-		const uint64_t tr = stats ? ReplayStats::now() : 0;
-		long n;
-		if (p->map) {
-			size_t end = 0;
-			if (ix_need(p)) {
-				build_index();
-				if (stats)
-					st.ix += ReplayStats::now() - tr;
-			}
-			n = scan_batch(p, FRAME_BYTES, x.desc, x.src, BATCH, &end);
-			if (stats)
-				st.scan += ReplayStats::now() - tr;
-			if (n > 0) {
-				x.n = (uint32_t)n;
-				memset(x.frames + end, 0, NSD_FRAME_PAD);
-				start_fill(x, k);
-			}
-		} else {
-			n = read_batch(p, x.frames, FRAME_BYTES, x.desc, x.sll, x.fh, BATCH, nullptr, nullptr, x.rhdr);
-		}
-		// the mapped batch before this one: its copy done, on to the device
-		// (file order)
-		if (pend >= 0) {
-			const int j = pend;
-			pend = -1;
-			wait_fill(b[j]);
-			const long r = submit_slot(j, pend_n);
-			if (r != NSD_OK) {
-				if (n > 0 && p->map)
-					wait_fill(x);
-				give_back(k);
-				rc = r;
-				break;
-			}
-		}
-		if (stats)
-			st.read += ReplayStats::now() - tr;
-		if (n == NSD_ERR_CAPLEN) {
-			give_back(k);
-			rc = one_big();
-			continue;
-		}
-		if (n <= 0) {
-			give_back(k);
-			if (n < 0)
-				rc = n;
-			break;
-		}
-		if (p->map) {
-			pend = k;
-			pend_n = n;
-			continue;
-		}
-		const long r = submit_slot(k, n);
-		if (r != NSD_OK) {
-			rc = r;
-			break;
-		}
-	}
-	if (ix_flight)
-		ix_join();   // (an index window no scan reached)
-	if (pend >= 0) {
-		// (left by an error: its copy drains before the slots go away)
-		wait_fill(b[pend]);
-		std::lock_guard<std::mutex> g(mu);
-		free_slots.push_back(pend);
-	}
-	{
-		const long r = flush_all();
-		if (rc == NSD_OK)
-			rc = r;
-	}
-	{
-		std::lock_guard<std::mutex> g(mu);
-		stop = true;
-	}
-	cv_job.notify_all();
-	cv_write.notify_all();
-	for (auto &t : pool)
-		t.join();
-	writer.join();
-	if (stats)
-		fprintf(stderr,
-			"nsd_replay: %ld records, %d threads, %.1f ms: read %.1f (scan %.1f, index %.1f), device waits %.1f, slot waits %.1f, "
-			"format %.1f (%llu jobs, %.1f per thread), write %.1f ms\n",
-			printed, threads, (ReplayStats::now() - t_start) / 1e6, st.read / 1e6, st.scan / 1e6, st.ix / 1e6, st.dev / 1e6, st.slot / 1e6,
-			st.fmt / 1e6, (unsigned long long)st.jobs.load(), st.fmt / 1e6 / threads, st.write / 1e6);
-	// (an error leaves batches in the pipe: drop the cached set then)
-	if (&res == &own || rc != NSD_OK)
-		res.release();
-	nsd_pcap_close(p);
-	return rc == NSD_OK ? printed : rc;
-}
-
-// dissector_cleanup_all (nsd_proto.cpp) frees the replay's cached buffers
-extern "C" __attribute__((visibility("hidden"))) void nsd_replay_release(void)
-{
-	std::lock_guard<std::mutex> g(g_replay_mu);
-	g_replay.release();
 }
 
 // ---- TPACKET_V3 ring front end (walk_t3_block, netsniff-ng.c:990-1039) ------

@@ -9,26 +9,10 @@
 #include <stdio.h>
 #include <string.h>
 
-#include "../../include/netsniff_dissect.h"
-
-extern "C" int nsd_launch_dissect_rec(const uint8_t *d_frames, const uint64_t *d_desc, const void *d_sll,
-				      uint32_t n, int start_id, int mode, void *d_rec, int compact, uint32_t *d_ext,
-				      uint32_t ext_words, uint32_t *d_ext_used, uint64_t *d_counters, void *d_ws,
-				      int grid, hipStream_t stream);
-extern "C" size_t nsd_launch_workspace_bytes(uint32_t n);
-int nsd_start_for(int linktype);
+#include "nsd_internal.h"
 
 namespace {
 constexpr int MAX_DEPTH = 8;
-
-bool ok(hipError_t e, const char *what)
-{
-	if (e != hipSuccess) {
-		fprintf(stderr, "netsniff-dissect pipe: %s: %s\n", what, hipGetErrorString(e));
-		return false;
-	}
-	return true;
-}
 
 // makes the pipe's device current for a scope (a caller that switched device
 // since the pipe was created still runs the pipe's batches where its buffers
@@ -150,16 +134,16 @@ static nsd_pipe *pipe_create(uint32_t max_pkts, size_t max_frame_bytes, uint32_t
 	p->compact = compact;
 	for (int k = 0; k < depth; k++) {
 		Slot &s = p->slot[k];
-		bool good = ok(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking), "stream") &&
-			    ok(hipEventCreateWithFlags(&s.done, hipEventDisableTiming), "event") &&
-			    ok(hipMalloc(&s.frames, max_frame_bytes + NSD_FRAME_PAD), "hipMalloc") &&
-			    ok(hipMalloc(&s.desc, (size_t)max_pkts * 8), "hipMalloc") &&
-			    ok(hipMalloc(&s.sll, (size_t)max_pkts * sizeof(nsd_sll_t)), "hipMalloc") &&
-			    ok(hipMalloc(&s.rec, (size_t)max_pkts * sizeof(nsd_rec)), "hipMalloc") &&
-			    (!ext_cap || ok(hipMalloc(&s.ext, (size_t)ext_cap * 4), "hipMalloc")) &&
-			    ok(hipMalloc(&s.small, 64 + NSD_NCOUNTERS * 8), "hipMalloc") &&
-			    ok(hipHostMalloc(&s.small_h, 64 + NSD_NCOUNTERS * 8, hipHostMallocDefault), "hipHostMalloc") &&
-			    ok(hipMalloc(&s.ws, nsd_launch_workspace_bytes(max_pkts)), "hipMalloc");
+		bool good = hip_ok(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking), "stream") &&
+			    hip_ok(hipEventCreateWithFlags(&s.done, hipEventDisableTiming), "event") &&
+			    hip_ok(hipMalloc(&s.frames, max_frame_bytes + NSD_FRAME_PAD), "hipMalloc") &&
+			    hip_ok(hipMalloc(&s.desc, (size_t)max_pkts * 8), "hipMalloc") &&
+			    hip_ok(hipMalloc(&s.sll, (size_t)max_pkts * sizeof(nsd_sll_t)), "hipMalloc") &&
+			    hip_ok(hipMalloc(&s.rec, (size_t)max_pkts * sizeof(nsd_rec)), "hipMalloc") &&
+			    (!ext_cap || hip_ok(hipMalloc(&s.ext, (size_t)ext_cap * 4), "hipMalloc")) &&
+			    hip_ok(hipMalloc(&s.small, 64 + NSD_NCOUNTERS * 8), "hipMalloc") &&
+			    hip_ok(hipHostMalloc(&s.small_h, 64 + NSD_NCOUNTERS * 8, hipHostMallocDefault), "hipHostMalloc") &&
+			    hip_ok(hipMalloc(&s.ws, nsd_launch_workspace_bytes(max_pkts)), "hipMalloc");
 		if (!good) {
 			nsd_pipe_destroy(p);
 			return nullptr;
@@ -173,7 +157,7 @@ static int complete_oldest(nsd_pipe *p)
 {
 	Slot &s = p->slot[p->head];
 	int st = s.status;
-	if (st == NSD_OK && !ok(hipEventSynchronize(s.done), "batch"))
+	if (st == NSD_OK && !hip_ok(hipEventSynchronize(s.done), "batch"))
 		st = NSD_ERR_HIP;
 	if (st == NSD_OK) {
 		const uint32_t used = (uint32_t)s.small_h[0];
@@ -188,10 +172,10 @@ static int complete_oldest(nsd_pipe *p)
 		const uint64_t need = p->compact ? (side ? (uint64_t)s.n + used : 0) : used;
 		const uint32_t k = need < p->ext_cap ? (uint32_t)need : p->ext_cap;
 		if (k && s.ext_out &&
-		    !ok(hipMemcpyAsync(s.ext_out, s.ext, (size_t)k * 4, hipMemcpyDeviceToHost,
+		    !hip_ok(hipMemcpyAsync(s.ext_out, s.ext, (size_t)k * 4, hipMemcpyDeviceToHost,
 				       s.stream), "ext D2H"))
 			st = NSD_ERR_HIP;
-		if (k && s.ext_out && st == NSD_OK && !ok(hipStreamSynchronize(s.stream), "ext D2H"))
+		if (k && s.ext_out && st == NSD_OK && !hip_ok(hipStreamSynchronize(s.stream), "ext D2H"))
 			st = NSD_ERR_HIP;
 	}
 	if (s.status_out)
@@ -290,31 +274,31 @@ static int pipe_submit(nsd_pipe *p, const uint8_t *frames, size_t frames_len, co
 	p->count++;
 	const hipStream_t st = s.stream;
 	const size_t rb = p->compact ? sizeof(nsd_crec) : sizeof(nsd_rec);
-	bool good = ok(hipMemsetAsync(s.small, 0, 64 + NSD_NCOUNTERS * 8, st), "memset");
+	bool good = hip_ok(hipMemsetAsync(s.small, 0, 64 + NSD_NCOUNTERS * 8, st), "memset");
 	if (good && n) {
-		good = ok(hipMemcpyAsync(s.frames, frames, frames_len, hipMemcpyHostToDevice, st), "H2D") &&
-		       ok(hipMemsetAsync(s.frames + frames_len, 0, NSD_FRAME_PAD, st), "memset") &&
-		       ok(hipMemcpyAsync(s.desc, desc, (size_t)n * 8, hipMemcpyHostToDevice, st), "H2D") &&
-		       (!sll || ok(hipMemcpyAsync(s.sll, sll, (size_t)n * sizeof(nsd_sll_t), hipMemcpyHostToDevice,
+		good = hip_ok(hipMemcpyAsync(s.frames, frames, frames_len, hipMemcpyHostToDevice, st), "H2D") &&
+		       hip_ok(hipMemsetAsync(s.frames + frames_len, 0, NSD_FRAME_PAD, st), "memset") &&
+		       hip_ok(hipMemcpyAsync(s.desc, desc, (size_t)n * 8, hipMemcpyHostToDevice, st), "H2D") &&
+		       (!sll || hip_ok(hipMemcpyAsync(s.sll, sll, (size_t)n * sizeof(nsd_sll_t), hipMemcpyHostToDevice,
 						  st), "H2D"));
 		good = good && nsd_launch_dissect_rec(s.frames, s.desc, sll ? s.sll : nullptr, n, p->start_id,
 						      p->mode, s.rec, p->compact ? 1 : 0, p->ext_cap ? s.ext : nullptr,
 						      p->ext_cap, s.small, (uint64_t *)((uint8_t *)s.small + 64), s.ws, 0,
 						      st) == 0;
-		good = good && ok(hipMemcpyAsync(rec, s.rec, (size_t)n * rb, hipMemcpyDeviceToHost, st), "D2H");
+		good = good && hip_ok(hipMemcpyAsync(rec, s.rec, (size_t)n * rb, hipMemcpyDeviceToHost, st), "D2H");
 	}
-	good = good && ok(hipMemcpyAsync(s.small_h, s.small, 64 + NSD_NCOUNTERS * 8, hipMemcpyDeviceToHost,
+	good = good && hip_ok(hipMemcpyAsync(s.small_h, s.small, 64 + NSD_NCOUNTERS * 8, hipMemcpyDeviceToHost,
 					 st), "D2H") &&
-	       ok(hipEventRecord(s.done, st), "event");
+	       hip_ok(hipEventRecord(s.done, st), "event");
 	if (!good)
 		s.status = NSD_ERR_HIP;
 	return good ? NSD_OK : NSD_ERR_HIP;
 }
 
 // point an idle pipe at another link type / print mode (the pcap replay keeps
-// one pipe for the process, nsd_pcap.cpp); 1 when the pipe lives on another
+// one pipe for the process, nsd_replay.cpp); 1 when the pipe lives on another
 // device than the current one (the replay then builds a set on this one)
-extern "C" __attribute__((visibility("hidden"))) int nsd_pipe_retarget(nsd_pipe *p, int linktype, int mode)
+extern "C" int nsd_pipe_retarget(nsd_pipe *p, int linktype, int mode)
 {
 	if (!p || p->count || mode < PRINT_NORM || mode > PRINT_NONE)
 		return NSD_ERR_ARG;

@@ -33,24 +33,8 @@
 
 #include <string>
 
-#include "../../include/netsniff_dissect.h"
+#include "nsd_internal.h"
 #include "nsd_lookup.h"
-
-namespace nsd {
-bool render_layer(std::string &s, const uint8_t *pkt, uint32_t caplen, int id, uint32_t start, uint32_t tail,
-		  int mode, uint16_t ip_csum, bool icmp_bad, const nsd_sll_t *sll, uint32_t &data,
-		  uint32_t &ntail, bool &next);
-void render_hex(std::string &s, const uint8_t *pkt, uint32_t caplen, uint32_t from, uint32_t len);
-void render_ascii(std::string &s, const uint8_t *pkt, uint32_t caplen, uint32_t from, uint32_t len);
-int cpu_step(int mode, const uint8_t *pkt, uint32_t caplen, int id, uint32_t &data, uint32_t &tail,
-	     uint16_t &ip_csum, uint8_t &flags, const nsd_sll_t *sll);
-int render_packet_cpu(std::string &text, const uint8_t *packet, size_t len, int linktype, int mode,
-		      const nsd_sll_t *sll);
-}
-
-extern "C" __attribute__((visibility("hidden"))) void nsd_device_ctx_release(void);
-extern "C" __attribute__((visibility("hidden"))) void nsd_replay_release(void);
-extern "C" __attribute__((visibility("hidden"))) void nsd_if_cache_reset(void);
 
 #ifndef NSD_ETCDIRE
 #define NSD_ETCDIRE "/etc/netsniff-ng"

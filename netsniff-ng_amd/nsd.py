@@ -839,7 +839,7 @@ def pcap_flows(path, table, mode=PRINT_NORM, prog=None):
     return n
 
 
-# ---- pcap replay front end (nsd_pcap.cpp) ---------------------------------------
+# ---- pcap replay front end (nsd_pcap.cpp the reader, nsd_replay.cpp the replay) ---------------------------------------
 def pcap_read(path, cap=64 << 20, max_n=1 << 16, sll=False):
     """Read a whole pcap through nsd_pcap_read_batch_sll: (linktype, [batches]),
     each batch = (frames uint8, desc uint64, wire_len uint32, ts_ns uint64)

@@ -1,5 +1,6 @@
-"""pcap replay front end (nsd_pcap.cpp; read_pcap netsniff-ng.c:640-770,
-pcap_io.h record formats, pcap_sg.c reader).
+"""pcap replay front end (nsd_pcap.cpp the reader, nsd_replay.cpp the replay
+that drives it; read_pcap netsniff-ng.c:640-770, pcap_io.h record formats,
+pcap_sg.c reader).
 
 CPU: the reader against the committed pcaps (tiny = C1, edge) in every record
 format the reference reads (usec / nsec / Kuznetzov / Borkmann magics, both
@@ -267,13 +268,14 @@ def replayable(name, mode, tmp_path):
     return path, keep
 
 
-def frame_lines(path, mode, accepted=None):
+def frame_lines(path, mode, accepted=None, read=None):
     """show_frame_hdr's line per replayed record (restated, pinned against
     the reference's pcap code in test_frame_hdr.py); with `accepted` (record
-    indexes a filter passes) only theirs, counted among themselves."""
-    lt = nsd.pcap_frame_hdrs(path)[0]
+    indexes a filter passes) only theirs, counted among themselves.  `read`:
+    the file's (linktype, packets) when the batch reader cannot give them (a
+    record above NSD_MAX_CAPLEN)."""
+    lt, pkts = read if read is not None else nsd.pcap_frame_hdrs(path)[:2]
     fh, sll, _ = T.oracle_pcap_meta(path)
-    _, pkts, _, _ = nsd.pcap_frame_hdrs(path)
     idx = range(len(fh)) if accepted is None else accepted
     return [T.oracle_frame_hdr(fh[i], sll[i], pkts[i], linktype=lt, mode=mode, count=k + 1)
             for k, i in enumerate(idx)]
@@ -550,3 +552,93 @@ def test_replay_pcap_out(tmp_path, fmt):
         n2, _ = nsd.replay_pcap(src, mode=T.PRINT_NORM, prog=prog, pcap_out=dst)
         assert n2 == keep.sum()
         assert open(dst, "rb").read() == want_hdr + b"".join(r for r, k in zip(recs, keep) if k)
+
+
+def _replay_bounded(**kw):
+    """nsd.replay_pcap on a thread joined with a timeout (a hang fails the
+    test instead of stalling it): the call's result, or the NsdError it
+    raised."""
+    import threading
+    out = {}
+
+    def run():
+        try:
+            out["ret"] = nsd.replay_pcap(**kw)
+        except nsd.NsdError as e:
+            out["err"] = e
+
+    t = threading.Thread(target=run, daemon=True)
+    t.start()
+    t.join(60)
+    assert not t.is_alive(), "the replay did not return"
+    return out
+
+
+def _edge_golden_text(path, keep, mode):
+    """The text test_replay_edge_matches_golden expects for replayable("edge")."""
+    gold = TG.load_golden(f"edge.m{mode}.w65535")
+    fl = frame_lines(path, mode)
+    return b"".join(fl[k] + gold[i] for k, i in enumerate(keep))
+
+
+@pytest.mark.gpu
+@pytest.mark.usefixtures("device_fill")
+@pytest.mark.parametrize("cols", [0, 80])
+def test_replay_text_write_error_then_recovery(tmp_path, cols):
+    """The text output fails (out_fd on /dev/full; cols=0 the writev path,
+    cols=80 the wrap path): the replay returns a negative status (no hang:
+    reader, pool and writer all wind down), and the next replay, which
+    rebuilds the cached staging dropped on the error, prints the golden text."""
+    path, keep = replayable("edge", T.PRINT_NORM, tmp_path)
+    fd = os.open("/dev/full", os.O_WRONLY)
+    try:
+        out = _replay_bounded(path=path, mode=T.PRINT_NORM, cols=cols, threads=1, out_fd=fd)
+    finally:
+        os.close(fd)
+    assert "err" in out and "ret" not in out
+    n, text = nsd.replay_pcap(path, mode=T.PRINT_NORM, threads=1, cols=65535)
+    assert n == len(keep) and text == _edge_golden_text(path, keep, T.PRINT_NORM)
+
+
+@pytest.mark.gpu
+@pytest.mark.usefixtures("device_fill")
+def test_replay_pcap_out_write_error(tmp_path):
+    """The `--out` file cannot be written (/dev/full): NsdError, and the next
+    replay is correct."""
+    path, keep = replayable("edge", T.PRINT_NORM, tmp_path)
+    out = _replay_bounded(path=path, mode=T.PRINT_NORM, threads=1, pcap_out="/dev/full")
+    assert "err" in out and "ret" not in out
+    n, text = nsd.replay_pcap(path, mode=T.PRINT_NORM, threads=1, cols=65535)
+    assert n == len(keep) and text == _edge_golden_text(path, keep, T.PRINT_NORM)
+
+
+@pytest.mark.gpu
+@pytest.mark.usefixtures("device_fill")
+def test_replay_big_filtered_pcap_out(tmp_path):
+    """Records above NSD_MAX_CAPLEN (big.pcap) with a filter and `--out`: the
+    over-long records go one by one through the filter and the per-packet
+    path, between the batches; only the accepted records print (counted among
+    themselves) and reach the written pcap, bytes as in the source."""
+    mode = T.PRINT_NORM
+    src = os.path.join(G, "big.pcap")
+    _, pkts = T.read_pcap(src)
+    # IPv6 only: ethertype 0x86DD (test_pcap_flows' program)
+    prog = nsd.BpfProgram(np.array([(0x28, 0, 0, 12), (0x15, 0, 1, 0x86DD), (0x06, 0, 0, 0xFFFF), (0x06, 0, 0, 0)],
+                                   dtype=nsd.BPF_INSN))
+    acc = [i for i, p in enumerate(pkts) if p[12:14] == b"\x86\xdd"]
+    assert acc and len(acc) < len(pkts) and any(len(pkts[i]) > 65535 for i in acc)
+    gold = TG.load_golden(f"big.m{mode}.w65535")
+    fl = frame_lines(src, mode, accepted=acc, read=(1, pkts))
+    # (the restated lines over this file are the reference's: its whole replay text)
+    assert b"".join(a + b for a, b in zip(frame_lines(src, mode, read=(1, pkts)), gold)) == \
+        b"".join(TG.load_golden(f"big.fh.m{mode}.w65535"))
+    dst = str(tmp_path / "out.pcap")
+    # (cols as the golden's: the over-long payload lines wrap at 65535 columns)
+    n, text = nsd.replay_pcap(src, mode=mode, prog=prog, cols=65535, pcap_out=dst)
+    prog.close()
+    assert n == len(acc) and text == b"".join(fl[k] + gold[i] for k, i in enumerate(acc))
+    data = open(src, "rb").read()
+    recs = _records(data, 16, "<")
+    assert len(recs) == len(pkts)
+    want_hdr = data[:16] + struct.pack("<II", 65535, 1)
+    assert open(dst, "rb").read() == want_hdr + b"".join(recs[i] for i in acc)
