@@ -759,6 +759,73 @@ long nsd_pcap_flows(const char *path, int mode, const struct nsd_bpf_prog *filte
 long nsd_flow_cpu(const uint8_t *frames, const nsd_desc_t *desc, uint32_t n, const nsd_rec *rec,
 		  const uint32_t *ext, uint64_t base, nsd_flow *flows, uint32_t max, uint64_t *stats);
 
+/* ---- conversations and top talkers from the flow table ---------------------
+ * flowtop's row is a conversation: struct flow_entry carries pkts_src /
+ * bytes_src and pkts_dst / bytes_dst, conntrack's ORIG and REPL counters.
+ * These entries pair the table's unidirectional flows and return the first k
+ * conversations of an order, so the answer to "which conversations carry the
+ * traffic" leaves the device as k rows.  They only read the table.
+ *
+ * Pairing:
+ *   The reverse of a flow is the key with src / dst and sport / dport
+ *   swapped, l3 / l4 unchanged (TCP A -> B never pairs with UDP B -> A; ICMP
+ *   and later-fragment flows, ports 0 / 0, pair by address like any other).
+ *   A flow and its reverse, when both are in the table, are one
+ *   conversation.  Its originator (src -> dst of the row, conntrack's ORIG)
+ *   is the direction with the smaller `first`; with reused `base` values and
+ *   equal `first`, the direction whose 40 key bytes compare smaller (memcmp).
+ *   A flow whose reverse is not in the table (never seen, or dropped as
+ *   FULL) is a conversation with the _dst fields zero.  So is a flow that is
+ *   its own reverse (src == dst, sport == dport); it is not counted twice.
+ * Order and selection:
+ *   NSD_CONV_BY_FIRST: first ascending; NSD_CONV_BY_BYTES: bytes_src +
+ *   bytes_dst descending, then first ascending; NSD_CONV_BY_PKTS: pkts_src +
+ *   pkts_dst descending, then first ascending.  k = the rows wanted; k >= the
+ *   table's conversations means all of them (UINT32_MAX is allowed).  The
+ *   selection is exact: the rows returned are the first k of the total order.
+ *   Rows equal in metric and `first` (reused bases only) have unspecified
+ *   relative order.
+ *
+ * nsd_flow_conv_device: all pointers are device pointers; it only enqueues on
+ * `stream` (no allocation, no host synchronisation, a linear chain:
+ * graph-capturable like nsd_flow_update_device) and must be ordered on the
+ * table's stream.  d_workspace (16-byte aligned) holds
+ * nsd_flow_conv_workspace_bytes(t) = 2048 + 24 * nsd_flow_slots(t) bytes.
+ * d_count[0] = the rows written = min(k, conversations), d_count[1] = the
+ * conversations in the table.  Exactly d_count[0] rows are written into
+ * d_conv (8-byte aligned), never a byte past them, in unspecified order (the
+ * set is exact).  NSD_ERR_ARG before anything is launched: NULL table, bad
+ * `by`, NULL or misaligned d_conv with k > 0, NULL d_count or d_workspace.
+ * nsd_flow_conversations: to host memory, synchronous, rows in the requested
+ * order; returns the table's conversation count (the first min(k, count) rows
+ * are written); stats may be NULL, else the table's NSD_FLOW_NSTATS words.
+ * Workspace and staging are allocated and freed inside the call, as in
+ * nsd_flow_export; what the table owns does not grow.
+ * nsd_conv_cpu: the same pairing and order on the host CPU over n nsd_flow
+ * rows in any order with unique keys (nsd_flow_cpu's or nsd_flow_export's);
+ * returns the conversation count (the first `max` rows are written).  For
+ * hosts without a GPU, and the in-product check of the pairing rules. */
+typedef struct nsd_conv {          /* 88 bytes; bytes 0..37: the originator's flow key, as nsd_flow */
+	uint8_t  src[16], dst[16];
+	uint16_t sport, dport;
+	uint8_t  l3, l4;
+	uint8_t  tcp_flags_src;    /* OR over src -> dst */
+	uint8_t  tcp_flags_dst;    /* OR over dst -> src */
+	uint64_t pkts_src, bytes_src;   /* src -> dst (flowtop's pkts_src / bytes_src) */
+	uint64_t pkts_dst, bytes_dst;   /* dst -> src; 0 when that flow is not in the table */
+	uint64_t first, last;      /* min first / max last over both directions */
+} nsd_conv;
+
+#define NSD_CONV_BY_FIRST 0   /* first ascending */
+#define NSD_CONV_BY_BYTES 1   /* bytes_src + bytes_dst descending, then first ascending */
+#define NSD_CONV_BY_PKTS  2   /* pkts_src + pkts_dst descending, then first ascending */
+
+size_t nsd_flow_conv_workspace_bytes(const nsd_flow_table *t);
+int  nsd_flow_conv_device(nsd_flow_table *t, int by, uint32_t k, nsd_conv *d_conv,
+			  uint32_t *d_count /* [2] */, void *d_workspace, void *stream);
+long nsd_flow_conversations(nsd_flow_table *t, int by, uint32_t k, nsd_conv *conv, uint64_t *stats);
+long nsd_conv_cpu(const nsd_flow *flows, size_t n, int by, nsd_conv *conv, uint32_t max);
+
 /* Pinned host memory for the pipe's buffers. */
 void *nsd_host_alloc(size_t len);
 void nsd_host_free(void *ptr);

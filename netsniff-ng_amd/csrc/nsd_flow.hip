@@ -26,6 +26,7 @@
 // the slots a flow's packet found taken by other flows stay so for every
 // later packet of that flow, and a packet that meets its flow's slot matches.
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -304,6 +305,341 @@ __global__ __launch_bounds__(BLOCK) void flow_export(Tab t, uint64_t *out, uint3
 		stats_out[threadIdx.x] = t.stats[threadIdx.x];
 }
 
+// ---- conversations and top-k ------------------------------------------------
+// A flow and its reverse (src / dst and sport / dport swapped) are one
+// conversation, owned by the direction seen first (the header's "pairing").
+// These kernels run after the commit on the table's stream and only read the
+// table: state is EMPTY or OCCUPIED, no atomics on it, no fences.
+//
+// Workspace: a CONV_HDR-byte header, then by candidate index four arrays of `slots` entries: hi u64 | lo u64 (the sort
+// key, larger is better) | slot u32 | rev u32 (the reverse's slot or NOSLOT).
+// conv_init zeroes the header: a kernel, not hipMemsetAsync - a memset
+// captured into a HIP graph does not reliably run on replay (DESIGN.md 4.1,
+// 4.8), and a header left as it was sends the later kernels past the
+// candidate arrays.  They bound what they read from the workspace by `slots`
+// all the same.
+constexpr size_t CONV_HDR = 2048;
+constexpr int CONV_DIGITS = 16;   // 8-bit digits of the 128-bit key, most significant first
+
+struct ConvHdr {
+	uint32_t ncand;      // candidates = conversations (conv_pair's cursor)
+	uint32_t rem;        // rows still wanted among the candidates that match `pre`
+	uint32_t n_above;    // conv_gather's cursor of rows above the threshold
+	uint32_t n_tied;     // ... and of rows equal to it
+	uint64_t pre[2];     // hi, lo: the digits decided so far; in the end the k-th key
+	uint64_t any1[2];    // OR of the keys
+	uint64_t any0[2];    // OR of the keys' complements
+	uint32_t bins[256];
+};
+static_assert(sizeof(ConvHdr) <= CONV_HDR && offsetof(ConvHdr, bins) % 16 == 0, "conv header");
+
+struct ConvWs {
+	ConvHdr *h;
+	uint64_t *hi, *lo;
+	uint32_t *slot, *rev;
+	uint32_t slots;
+};
+
+__global__ __launch_bounds__(BLOCK) void conv_init(ConvWs w)
+{
+	for (uint32_t i = threadIdx.x; i < sizeof(ConvHdr) / 4; i += BLOCK)
+		((uint32_t *)w.h)[i] = 0;
+}
+
+// the candidates: conv_pair's cursor, never more than the slots
+__device__ __forceinline__ uint32_t conv_ncand(const ConvWs &w)
+{
+	const uint32_t n = w.h->ncand;
+	return n < w.slots ? n : w.slots;
+}
+
+__device__ __forceinline__ void load_key(const Tab &t, uint32_t s, Key &k)
+{
+	const uint64_t *kp = t.key + 5ull * s;
+	for (int j = 0; j < 5; j++)
+		k.w[j] = kp[j];
+}
+
+// memcmp of the 40 key bytes: the words are little-endian images of them
+__device__ __forceinline__ bool key_bytes_less(const Key &a, const Key &b)
+{
+	for (int j = 0; j < 5; j++)
+		if (a.w[j] != b.w[j])
+			return __builtin_bswap64(a.w[j]) < __builtin_bswap64(b.w[j]);
+	return false;
+}
+
+// One slot per lane, grid-stride.  The slot that owns its conversation emits
+// a candidate through a wave-aggregated cursor; the OR of the keys and of
+// their complements (which digits differ at all) is combined per thread, then
+// per block in LDS, and reaches the header once per block.
+__global__ __launch_bounds__(BLOCK) void conv_pair(Tab t, ConvWs w, int by)
+{
+	__shared__ unsigned long long red[4];
+	if (threadIdx.x < 4)
+		red[threadIdx.x] = 0;
+	__syncthreads();
+	const uint32_t lane = threadIdx.x & 63;
+	const uint32_t mask = t.slots - 1;
+	const uint64_t stride = (uint64_t)gridDim.x * BLOCK;
+	uint64_t o1h = 0, o1l = 0, o0h = 0, o0l = 0;
+#pragma unroll 1
+	for (uint64_t s0 = (uint64_t)blockIdx.x * BLOCK + (threadIdx.x & ~63u); s0 < t.slots; s0 += stride) {
+		const uint64_t s = s0 + lane;
+		const bool occ = s < t.slots && t.state[s] == OCCUPIED;
+		bool own = false;
+		uint32_t rev = NOSLOT;
+		uint64_t hi = 0, lo = 0;
+		if (occ) {
+			Key k, r;
+			load_key(t, (uint32_t)s, k);
+			r.w[0] = k.w[2];
+			r.w[1] = k.w[3];
+			r.w[2] = k.w[0];
+			r.w[3] = k.w[1];
+			r.w[4] = (k.w[4] & ~0xFFFFFFFFull) | (k.w[4] & 0xFFFFu) << 16 | (k.w[4] >> 16 & 0xFFFFu);
+			const Cnt c = t.cnt[s];
+			uint64_t metric = by == NSD_CONV_BY_PKTS ? c.pkts : c.bytes;
+			own = true;
+			if (!key_eq(k, r)) {
+				uint32_t p = (uint32_t)key_hash(r) & mask;
+#pragma unroll 1
+				for (uint32_t probes = 0; probes < t.slots; probes++, p = (p + 1) & mask) {
+					const uint32_t v = t.state[p];
+					if (v == EMPTY)
+						break;
+					if (v != OCCUPIED)
+						continue;
+					Key o;
+					load_key(t, p, o);
+					if (key_eq(o, r)) {
+						rev = p;
+						break;
+					}
+				}
+				if (rev != NOSLOT) {
+					const Cnt d = t.cnt[rev];
+					own = c.first < d.first || (c.first == d.first && key_bytes_less(k, r));
+					metric += by == NSD_CONV_BY_PKTS ? d.pkts : d.bytes;
+				}
+			}
+			// (the owner's `first` is the conversation's: the smaller of the two)
+			if (by == NSD_CONV_BY_FIRST)
+				hi = ~c.first;
+			else
+				hi = metric, lo = ~c.first;
+		}
+		const uint64_t m = __ballot(own);
+		if (!m)
+			continue;
+		uint32_t at = 0;
+		if (lane == 0)
+			at = __hip_atomic_fetch_add(&w.h->ncand, (uint32_t)__popcll(m), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		at = __shfl(at, 0, 64);
+		if (own) {
+			const uint64_t pos = (uint64_t)at + (uint32_t)__popcll(m & ((1ull << lane) - 1));
+			if (pos < t.slots) {
+				w.hi[pos] = hi;
+				w.lo[pos] = lo;
+				w.slot[pos] = (uint32_t)s;
+				w.rev[pos] = rev;
+			}
+			o1h |= hi;
+			o1l |= lo;
+			o0h |= ~hi;
+			o0l |= ~lo;
+		}
+	}
+	if (o1h | o0h) {   // (a thread that emitted has a bit in one of the two)
+		atomicOr(&red[0], (unsigned long long)o1h);
+		atomicOr(&red[1], (unsigned long long)o1l);
+		atomicOr(&red[2], (unsigned long long)o0h);
+		atomicOr(&red[3], (unsigned long long)o0l);
+	}
+	__syncthreads();
+	if (threadIdx.x < 4 && red[threadIdx.x]) {
+		uint64_t *dst = threadIdx.x < 2 ? &w.h->any1[threadIdx.x] : &w.h->any0[threadIdx.x - 2];
+		(void)__hip_atomic_fetch_or(dst, (uint64_t)red[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+	}
+}
+
+// digit d (0 = most significant) of a key, and the key's digits above it
+__device__ __forceinline__ uint32_t conv_digit(uint64_t hi, uint64_t lo, int d)
+{
+	return (uint32_t)((d < 8 ? hi : lo) >> (8 * (7 - (d & 7)))) & 255u;
+}
+__device__ __forceinline__ bool conv_above_match(uint64_t hi, uint64_t lo, const uint64_t pre[2], int d)
+{
+	// mask of the digits 0 .. d-1
+	const uint64_t mh = d >= 8 ? ~0ull : d == 0 ? 0ull : ~0ull << (8 * (8 - d));
+	const uint64_t ml = d <= 8 ? 0ull : ~0ull << (8 * (16 - d));
+	return (((hi ^ pre[0]) & mh) | ((lo ^ pre[1]) & ml)) == 0;
+}
+// a digit on which all candidates agree is decided without a pass
+__device__ __forceinline__ bool conv_uniform(const ConvHdr *h, int d)
+{
+	return conv_digit(h->any1[0] & h->any0[0], h->any1[1] & h->any0[1], d) == 0;
+}
+
+// Histogram of digit d over the candidates that match the digits decided so
+// far: per-block bins in LDS, flushed once.  The high digits of a byte count
+// are the same for nearly every candidate - 64 lanes on one LDS bin - so a
+// wave first counts the lanes that share its first active lane's digit
+// (ballot / popcount, one add) and only the others add for themselves.
+__global__ __launch_bounds__(BLOCK) void conv_hist(ConvWs w, uint32_t k, int d)
+{
+	__shared__ uint32_t bins[256];
+	const ConvHdr *h = w.h;
+	const uint32_t n = conv_ncand(w);
+	if (n <= k || conv_uniform(h, d) || (uint64_t)blockIdx.x * BLOCK >= n)
+		return;   // (block-uniform)
+	bins[threadIdx.x] = 0;
+	__syncthreads();
+	const uint64_t pre[2] = { h->pre[0], h->pre[1] };
+	const uint32_t lane = threadIdx.x & 63;
+	const uint64_t stride = (uint64_t)gridDim.x * BLOCK;
+#pragma unroll 1
+	for (uint64_t i0 = (uint64_t)blockIdx.x * BLOCK + (threadIdx.x & ~63u); i0 < n; i0 += stride) {
+		const uint64_t i = i0 + lane;
+		bool act = false;
+		uint32_t dg = 0;
+		if (i < n) {
+			const uint64_t hi = w.hi[i], lo = d > 7 ? w.lo[i] : 0;
+			act = conv_above_match(hi, lo, pre, d);
+			dg = conv_digit(hi, lo, d);
+		}
+		const uint64_t m = __ballot(act);
+		if (!m)
+			continue;
+		const uint32_t lead = (uint32_t)__ffsll((long long)m) - 1;
+		const uint32_t d0 = __shfl(dg, lead, 64);
+		const uint64_t same = __ballot(act && dg == d0);
+		if (lane == lead)
+			atomicAdd(&bins[d0], (uint32_t)__popcll(same));
+		else if (act && dg != d0)
+			atomicAdd(&bins[dg], 1u);
+	}
+	__syncthreads();
+	const uint32_t c = bins[threadIdx.x];
+	if (c)
+		(void)__hip_atomic_fetch_add(&w.h->bins[threadIdx.x], c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// One wave: the bin where the count from the top crosses the rows still
+// wanted becomes digit d of the threshold; the bins are cleared for the next
+// digit.  Lane l holds bins 4l .. 4l+3.
+__global__ __launch_bounds__(64) void conv_scan(ConvWs w, uint32_t k, int d)
+{
+	ConvHdr *h = w.h;
+	if (conv_ncand(w) <= k)
+		return;
+	const uint32_t lane = threadIdx.x;
+	const uint32_t rem = d == 0 ? k : h->rem;
+	const int shift = 8 * (7 - (d & 7));
+	uint64_t *pre = &h->pre[d < 8 ? 0 : 1];
+	if (conv_uniform(h, d)) {
+		if (lane == 0) {
+			*pre |= (uint64_t)conv_digit(h->any1[0], h->any1[1], d) << shift;
+			h->rem = rem;
+		}
+		return;
+	}
+	uint4 *bp = (uint4 *)h->bins + lane;
+	const uint4 b = *bp;
+	const uint32_t mine = b.x + b.y + b.z + b.w;
+	uint32_t v = mine;   // -> the sum over lanes >= this one
+	for (uint32_t off = 1; off < 64; off <<= 1) {
+		const uint32_t u = __shfl_down(v, off, 64);
+		if (lane + off < 64)
+			v += u;
+	}
+	uint32_t run = v - mine;   // candidates in bins above this lane's
+	const uint32_t c[4] = { b.x, b.y, b.z, b.w };
+	for (int j = 3; j >= 0; j--) {
+		if (run < rem && rem - run <= c[j]) {
+			*pre |= (uint64_t)(4 * lane + j) << shift;
+			h->rem = rem - run;
+		}
+		run += c[j];
+	}
+	*bp = make_uint4(0, 0, 0, 0);
+}
+
+// Candidates above the threshold, and `rem` of those equal to it (more can tie
+// only when bases were reused), write their row: positions 0 .. k - rem - 1
+// and k - rem .. k - 1, each through a wave-aggregated cursor.
+__global__ __launch_bounds__(BLOCK) void conv_gather(Tab t, ConvWs w, uint32_t k, uint64_t *out, uint32_t *count)
+{
+	ConvHdr *h = w.h;
+	const uint32_t n = conv_ncand(w);
+	if (blockIdx.x == 0 && threadIdx.x == 0) {
+		count[0] = n < k ? n : k;
+		count[1] = n;
+	}
+	if (k == 0)
+		return;
+	const bool all = n <= k;
+	const uint64_t th = h->pre[0], tl = h->pre[1];
+	const uint32_t rem = all ? 0 : h->rem, base = all ? 0 : k - rem;
+	const uint32_t lane = threadIdx.x & 63;
+	const uint64_t stride = (uint64_t)gridDim.x * BLOCK, below = (1ull << lane) - 1;
+#pragma unroll 1
+	for (uint64_t i0 = (uint64_t)blockIdx.x * BLOCK + (threadIdx.x & ~63u); i0 < n; i0 += stride) {
+		const uint64_t i = i0 + lane;
+		bool above = false, tied = false;
+		if (i < n) {
+			const uint64_t hi = w.hi[i], lo = w.lo[i];
+			above = all || hi > th || (hi == th && lo > tl);
+			tied = !all && hi == th && lo == tl;
+		}
+		const uint64_t ma = __ballot(above), mt = __ballot(tied);
+		uint32_t a0 = 0, t0 = 0;
+		if (lane == 0) {
+			if (ma)
+				a0 = __hip_atomic_fetch_add(&h->n_above, (uint32_t)__popcll(ma), __ATOMIC_RELAXED,
+							    __HIP_MEMORY_SCOPE_AGENT);
+			if (mt)
+				t0 = __hip_atomic_fetch_add(&h->n_tied, (uint32_t)__popcll(mt), __ATOMIC_RELAXED,
+							    __HIP_MEMORY_SCOPE_AGENT);
+		}
+		a0 = __shfl(a0, 0, 64);
+		t0 = __shfl(t0, 0, 64);
+		uint64_t pos = UINT64_MAX;
+		if (above)
+			pos = (uint64_t)a0 + (uint32_t)__popcll(ma & below);
+		if (tied) {
+			const uint64_t j = (uint64_t)t0 + (uint32_t)__popcll(mt & below);
+			if (j < rem)
+				pos = base + j;
+		}
+		if (pos >= k)
+			continue;
+		const uint32_t s = w.slot[i], r = w.rev[i];
+		if (s >= t.slots || (r != NOSLOT && r >= t.slots))
+			continue;
+		const uint64_t *kp = t.key + 5ull * s;
+		const Cnt c = t.cnt[s];
+		Cnt e;
+		e.pkts = e.bytes = e.last = 0;
+		e.first = UINT64_MAX;
+		e.flags = 0;
+		if (r != NOSLOT)
+			e = t.cnt[r];
+		uint64_t *o = out + 11ull * pos;
+		o[0] = kp[0];
+		o[1] = kp[1];
+		o[2] = kp[2];
+		o[3] = kp[3];
+		o[4] = kp[4] | (uint64_t)(c.flags & 0xFFu) << 48 | (uint64_t)(e.flags & 0xFFu) << 56;
+		o[5] = c.pkts;
+		o[6] = c.bytes;
+		o[7] = e.pkts;
+		o[8] = e.bytes;
+		o[9] = c.first < e.first ? c.first : e.first;
+		o[10] = c.last > e.last ? c.last : e.last;
+	}
+}
+
 // device staging of the host-memory entries (nsd_flow_batch, nsd_pcap_flows),
 // grown on demand and kept with the table
 struct Stage {
@@ -484,6 +820,97 @@ extern "C" long nsd_flow_export(nsd_flow_table *t, nsd_flow *flows, uint32_t max
 	return (long)have;
 }
 
+// ---- conversations: the entries ---------------------------------------------
+static_assert(sizeof(nsd_conv) == 88 && offsetof(nsd_conv, pkts_src) == 40, "nsd_conv");
+
+extern "C" size_t nsd_flow_conv_workspace_bytes(const nsd_flow_table *t)
+{
+	return t ? CONV_HDR + 24 * (size_t)t->tab.slots : 0;
+}
+
+// init | pair | per digit: hist, scan | gather: a linear chain of kernels on `stream`
+extern "C" int nsd_flow_conv_device(nsd_flow_table *t, int by, uint32_t k, nsd_conv *d_conv, uint32_t *d_count,
+				    void *d_workspace, void *stream)
+{
+	if (!t || by < NSD_CONV_BY_FIRST || by > NSD_CONV_BY_PKTS || !d_count || !d_workspace ||
+	    (k && !d_conv) || ((uintptr_t)d_conv & 7) || ((uintptr_t)d_workspace & 15) || ((uintptr_t)d_count & 3))
+		return NSD_ERR_ARG;
+	hipStream_t s = (hipStream_t)stream;
+	const size_t slots = t->tab.slots;
+	uint8_t *m = (uint8_t *)d_workspace;
+	ConvWs w;
+	w.h = (ConvHdr *)m;
+	w.hi = (uint64_t *)(m + CONV_HDR);
+	w.lo = w.hi + slots;
+	w.slot = (uint32_t *)(w.lo + slots);
+	w.rev = w.slot + slots;
+	w.slots = t->tab.slots;
+	const dim3 grid(grid_for(t, slots)), block(BLOCK);
+	hipLaunchKernelGGL(conv_init, dim3(1), block, 0, s, w);
+	hipLaunchKernelGGL(conv_pair, grid, block, 0, s, t->tab, w, by);
+	if (k && k < slots) {   // (k >= slots: every conversation is wanted)
+		const int digits = by == NSD_CONV_BY_FIRST ? CONV_DIGITS / 2 : CONV_DIGITS;
+		for (int d = 0; d < digits; d++) {
+			hipLaunchKernelGGL(conv_hist, grid, block, 0, s, w, k, d);
+			hipLaunchKernelGGL(conv_scan, dim3(1), dim3(64), 0, s, w, k, d);
+		}
+	}
+	hipLaunchKernelGGL(conv_gather, grid, block, 0, s, t->tab, w, k, (uint64_t *)d_conv, d_count);
+	t->last = s;
+	return hip_ok(hipGetLastError(), "launch") ? NSD_OK : NSD_ERR_HIP;
+}
+
+// the total order of the header: `by`'s metric descending, then first ascending
+static void sort_conv(std::vector<nsd_conv> &v, int by)
+{
+	std::sort(v.begin(), v.end(), [by](const nsd_conv &a, const nsd_conv &b) {
+		if (by != NSD_CONV_BY_FIRST) {
+			const uint64_t ma = by == NSD_CONV_BY_BYTES ? a.bytes_src + a.bytes_dst : a.pkts_src + a.pkts_dst;
+			const uint64_t mb = by == NSD_CONV_BY_BYTES ? b.bytes_src + b.bytes_dst : b.pkts_src + b.pkts_dst;
+			if (ma != mb)
+				return ma > mb;
+		}
+		return a.first < b.first;
+	});
+}
+
+extern "C" long nsd_flow_conversations(nsd_flow_table *t, int by, uint32_t k, nsd_conv *conv, uint64_t *stats)
+{
+	if (!t || by < NSD_CONV_BY_FIRST || by > NSD_CONV_BY_PKTS || (k && !conv))
+		return NSD_ERR_ARG;
+	hipStream_t s = t->last;
+	uint64_t st[NSD_FLOW_NSTATS];
+	if (!hip_ok(hipMemcpyAsync(st, t->tab.stats, sizeof(st), hipMemcpyDeviceToHost, s), "D2H") ||
+	    !hip_ok(hipStreamSynchronize(s), "sync"))
+		return NSD_ERR_HIP;
+	// (no more conversations than flows)
+	const uint32_t have = (uint32_t)st[NSD_FLOW_ST_FLOWS], want = k < have ? k : have;
+	const size_t o_rows = 256, o_ws = (o_rows + (size_t)want * sizeof(nsd_conv) + 255) & ~(size_t)255;
+	uint8_t *d = nullptr;
+	if (!hip_ok(hipMalloc(&d, o_ws + nsd_flow_conv_workspace_bytes(t)), "hipMalloc"))
+		return NSD_ERR_NOMEM;
+	uint32_t *d_count = (uint32_t *)d;
+	nsd_conv *d_rows = (nsd_conv *)(d + o_rows);
+	uint32_t count[2] = { 0, 0 };
+	std::vector<nsd_conv> rows;
+	bool ok = nsd_flow_conv_device(t, by, want, d_rows, d_count, d + o_ws, s) == NSD_OK &&
+		  hip_ok(hipMemcpyAsync(count, d_count, 8, hipMemcpyDeviceToHost, s), "D2H") &&
+		  hip_ok(hipStreamSynchronize(s), "sync") && count[0] <= want;
+	if (ok && count[0]) {
+		rows.resize(count[0]);
+		ok = hip_ok(hipMemcpy(rows.data(), d_rows, (size_t)count[0] * sizeof(nsd_conv), hipMemcpyDeviceToHost), "D2H");
+	}
+	(void)hipFree(d);
+	if (!ok)
+		return NSD_ERR_HIP;
+	sort_conv(rows, by);
+	if (!rows.empty())
+		memcpy(conv, rows.data(), rows.size() * sizeof(nsd_conv));
+	if (stats)
+		memcpy(stats, st, sizeof(st));
+	return (long)count[1];
+}
+
 // ---- the same aggregation on the host -----------------------------------
 namespace {
 struct KeyHash {
@@ -537,6 +964,58 @@ extern "C" long nsd_flow_cpu(const uint8_t *frames, const nsd_desc_t *desc, uint
 		memcpy(flows, rows.data(), k * sizeof(nsd_flow));
 	if (stats)
 		memcpy(stats, st, sizeof(st));
+	return (long)rows.size();
+}
+
+// Flow rows (unique keys, any order) paired into conversations on the host:
+// a hash map from key to row, one lookup of the reverse per row.
+extern "C" long nsd_conv_cpu(const nsd_flow *flows, size_t n, int by, nsd_conv *conv, uint32_t max)
+{
+	if (by < NSD_CONV_BY_FIRST || by > NSD_CONV_BY_PKTS || (n && !flows) || (max && !conv))
+		return NSD_ERR_ARG;
+	auto key_of = [](const nsd_flow &f) {
+		Key k;
+		memcpy(k.w, &f, 40);
+		k.w[4] &= 0x0000FFFFFFFFFFFFull;   // tcp_flags, rsvd
+		return k;
+	};
+	std::unordered_map<Key, size_t, KeyHash, KeyEq> map;
+	map.reserve(n);
+	for (size_t i = 0; i < n; i++)
+		map.emplace(key_of(flows[i]), i);
+	std::vector<nsd_conv> rows;
+	for (size_t i = 0; i < n; i++) {
+		const nsd_flow &f = flows[i];
+		nsd_flow r = f;
+		memcpy(r.src, f.dst, 16);
+		memcpy(r.dst, f.src, 16);
+		r.sport = f.dport;
+		r.dport = f.sport;
+		const Key k = key_of(f), kr = key_of(r);
+		const auto it = key_eq(k, kr) ? map.end() : map.find(kr);
+		const nsd_flow *g = it == map.end() ? nullptr : &flows[it->second];
+		if (g && (g->first < f.first || (g->first == f.first && memcmp(kr.w, k.w, 40) < 0)))
+			continue;   // the reverse is the originator: its row carries this one
+		nsd_conv c;
+		memset(&c, 0, sizeof(c));
+		memcpy(&c, k.w, 40);
+		c.tcp_flags_src = f.tcp_flags;
+		c.pkts_src = f.pkts;
+		c.bytes_src = f.bytes;
+		c.first = f.first;
+		c.last = f.last;
+		if (g) {
+			c.tcp_flags_dst = g->tcp_flags;
+			c.pkts_dst = g->pkts;
+			c.bytes_dst = g->bytes;
+			c.last = g->last > f.last ? g->last : f.last;
+		}
+		rows.push_back(c);
+	}
+	sort_conv(rows, by);
+	const size_t k = rows.size() < max ? rows.size() : max;
+	if (k)
+		memcpy(conv, rows.data(), k * sizeof(nsd_conv));
 	return (long)rows.size();
 }
 

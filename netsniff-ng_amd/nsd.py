@@ -128,7 +128,8 @@ ABI_SYMBOLS = ["dissector_init_all", "dissector_entry_point", "dissector_cleanup
                "nsd_pcap_read_batch_fh", "nsd_t3_block_desc_fh", "nsd_pcap_index", "nsd_set_grid_cap",
                "nsd_set_record_ring", "nsd_set_debug_fill", "nsd_flow_create", "nsd_flow_destroy",
                "nsd_flow_slots", "nsd_flow_reset", "nsd_flow_update_device", "nsd_flow_export_device",
-               "nsd_flow_export", "nsd_flow_batch", "nsd_pcap_flows", "nsd_flow_cpu"]
+               "nsd_flow_export", "nsd_flow_batch", "nsd_pcap_flows", "nsd_flow_cpu",
+               "nsd_flow_conv_workspace_bytes", "nsd_flow_conv_device", "nsd_flow_conversations", "nsd_conv_cpu"]
 
 # struct sockaddr_ll (nsd_sll_t), one per packet for LINKTYPE_LINUX_SLL batches
 SLL_DTYPE = np.dtype([("family", "<u2"), ("protocol", ">u2"), ("ifindex", "<i4"), ("hatype", "<u2"),
@@ -147,6 +148,14 @@ FLOW_DTYPE = np.dtype([("src", "u1", (16,)), ("dst", "u1", (16,)), ("sport", "<u
 FLOW_BYTES = 72
 FLOW_NSTATS = 8
 FLOW_ST_PKTS, FLOW_ST_KEYED, FLOW_ST_NOIP, FLOW_ST_SKIPPED, FLOW_ST_FULL, FLOW_ST_FLOWS = range(6)
+
+# nsd_conv: one conversation (bytes 0..37 are the originator's flow key)
+CONV_DTYPE = np.dtype([("src", "u1", (16,)), ("dst", "u1", (16,)), ("sport", "<u2"), ("dport", "<u2"),
+                       ("l3", "u1"), ("l4", "u1"), ("tcp_flags_src", "u1"), ("tcp_flags_dst", "u1"),
+                       ("pkts_src", "<u8"), ("bytes_src", "<u8"), ("pkts_dst", "<u8"), ("bytes_dst", "<u8"),
+                       ("first", "<u8"), ("last", "<u8")])
+CONV_BYTES = 88
+CONV_BY_FIRST, CONV_BY_BYTES, CONV_BY_PKTS = range(3)
 
 _lib = None
 _vp, _u32, _u64, _int, _sz = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int, ctypes.c_size_t
@@ -284,6 +293,10 @@ def lib():
                 ("nsd_flow_batch", ctypes.c_long, [_vp, _sz, _vp, _u32, _int, _int, _vp, _u32, _vp]),
                 ("nsd_pcap_flows", ctypes.c_long, [ctypes.c_char_p, _int, _vp, _vp]),
                 ("nsd_flow_cpu", ctypes.c_long, [_vp, _vp, _u32, _vp, _vp, _u64, _vp, _u32, _vp]),
+                ("nsd_flow_conv_workspace_bytes", _sz, [_vp]),
+                ("nsd_flow_conv_device", _int, [_vp, _int, _u32, _vp, _vp, _vp, _vp]),
+                ("nsd_flow_conversations", ctypes.c_long, [_vp, _int, _u32, _vp, _vp]),
+                ("nsd_conv_cpu", ctypes.c_long, [_vp, _sz, _int, _vp, _u32]),
                 ("nsd_last_schedule", _int, [])):
             if hasattr(L, name):
                 getattr(L, name).restype = res
@@ -789,6 +802,35 @@ class FlowTable:
         _check(0 if n >= 0 else n, "nsd_flow_export")
         return flows[:min(n, cap)], stats
 
+    def conversations_device(self, by, k, conv=None, count=None, workspace=None, stream=None):
+        """The first k conversations of order `by` (nsd_flow_conv_device):
+        (conv u8[k*88], count i32[2] = rows written, conversations in the
+        table) cuda tensors; row order unspecified.  k = None: all."""
+        import torch
+        if k is None:
+            k = 0xFFFFFFFF
+        if conv is None:
+            conv = torch.empty(min(k, self.slots) * CONV_BYTES, dtype=torch.uint8, device="cuda")
+        if count is None:
+            count = torch.zeros(2, dtype=torch.int32, device=conv.device)
+        if workspace is None:
+            workspace = torch.empty(self.L.nsd_flow_conv_workspace_bytes(self.h), dtype=torch.uint8,
+                                    device=conv.device)
+        rc = self.L.nsd_flow_conv_device(self.h, by, k, conv.data_ptr(), count.data_ptr(), workspace.data_ptr(),
+                                         self._stream(stream, conv.device))
+        _check(rc, "nsd_flow_conv_device")
+        return conv, count
+
+    def conversations(self, by=CONV_BY_BYTES, k=None):
+        """(conv CONV_DTYPE, the first k of order `by`, in order; stats
+        u64[8]) in host memory (nsd_flow_conversations); synchronous."""
+        cap = self.slots if k is None else min(k, self.slots)
+        conv = np.zeros(max(cap, 1), dtype=CONV_DTYPE)
+        stats = np.zeros(FLOW_NSTATS, dtype=np.uint64)
+        n = self.L.nsd_flow_conversations(self.h, by, cap, conv.ctypes.data, stats.ctypes.data)
+        _check(0 if n >= 0 else n, "nsd_flow_conversations")
+        return conv[:min(n, cap)], stats
+
     def close(self):
         if getattr(self, "h", None):
             self.L.nsd_flow_destroy(self.h)
@@ -828,6 +870,17 @@ def flow_cpu(frames, desc, rec, ext=None, base=0, max_flows=None):
                            stats.ctypes.data)
     _check(0 if n >= 0 else n, "nsd_flow_cpu")
     return flows[:min(n, cap)], stats
+
+
+def conv_cpu(flows, by=CONV_BY_FIRST, max_conv=None):
+    """Flow rows (FLOW_DTYPE, any order, unique keys) paired into
+    conversations on the host CPU (nsd_conv_cpu): CONV_DTYPE in order `by`."""
+    flows = np.ascontiguousarray(flows, dtype=FLOW_DTYPE)
+    cap = len(flows) if max_conv is None else max_conv
+    conv = np.zeros(max(cap, 1), dtype=CONV_DTYPE)
+    n = lib().nsd_conv_cpu(flows.ctypes.data, len(flows), by, conv.ctypes.data, cap)
+    _check(0 if n >= 0 else n, "nsd_conv_cpu")
+    return conv[:min(n, cap)]
 
 
 def pcap_flows(path, table, mode=PRINT_NORM, prog=None):

@@ -24,6 +24,9 @@ Per workload, with HIP events around each call on one resident batch and a
 Rates are packets over the median time; bytes_per_packet is what an update has to move at
 least (model below), achieved_GBps that over the median.
 
+tools/flowbench_conv.py is a further leg on the same tables: conversations /
+top-k (nsd_flow_conv_device) beside a whole-table export and host sort.
+
 The result (one JSON object per workload and a merged flowbench.json) goes
 to --out (default bench_out/flowbench).
 """
@@ -57,17 +60,14 @@ def update_bytes_per_packet(counters, n):
     return 8 + 16 + key + 4 + 40 + 36
 
 
-def run_one(args):
+def workload_batch(name, n, dev):
+    """(frames, desc) of one workload on the device (the table in the module's docstring)."""
     import numpy as np
     import torch
-    import nsd
     import nsd_testlib as T
-    torch.cuda.set_device(0)
-    dev = torch.device("cuda", 0)
-    n = args.packets
-    cfg = {"udp64": T.SYN_UDP64, "imix": T.SYN_IMIX, "ipv6x": T.SYN_IPV6X, "heavy": T.SYN_UDP64}[args.one]
+    cfg = {"udp64": T.SYN_UDP64, "imix": T.SYN_IMIX, "ipv6x": T.SYN_IPV6X, "heavy": T.SYN_UDP64}[name]
     frames, desc, hdesc = T.make_device_batch(cfg, n, device=dev)
-    if args.one == "heavy":
+    if name == "heavy":
         assert (T.desc_caplen(hdesc) == 64).all() and (np.diff(T.desc_off(hdesc)) == 64).all()
         g = torch.Generator(device=dev)
         g.manual_seed(0x5EED)
@@ -77,6 +77,18 @@ def run_one(args):
         v[:, 28], v[:, 29] = (flow >> 8).to(torch.uint8), (flow & 255).to(torch.uint8)
         v[:, 34], v[:, 35] = 4, 0        # (C2's source port varies with i: one port for all)
         del flow, v
+    return frames, desc
+
+
+def run_one(args):
+    import numpy as np
+    import torch
+    import nsd
+    import nsd_testlib as T
+    torch.cuda.set_device(0)
+    dev = torch.device("cuda", 0)
+    n = args.packets
+    frames, desc = workload_batch(args.one, n, dev)
     L = nsd.lib()
     rec = torch.empty(n * nsd.REC_BYTES, dtype=torch.uint8, device=dev)
     ext = torch.empty(nsd.ext_pool_words(n) if args.one == "ipv6x" else 1 << 20, dtype=torch.int32, device=dev)
