@@ -698,7 +698,10 @@ int nsd_bpf_filter_batch(const nsd_bpf_prog *prog, const uint8_t *frames, size_t
  *       TCP packets that are no later fragments.
  * stats: PKTS = KEYED + NOIP + SKIPPED; FULL (a subset of KEYED) are packets
  * dropped because every slot was taken by other flows - a flow is in the
- * table with all its packets or not at all; FLOWS = the flows in the table.
+ * table with all its packets since it entered or not at all (it enters with
+ * its first packet that finds a slot; nsd_flow_expire_* below lets it leave);
+ * FLOWS = the flows in the table; EXPIRED = the flows nsd_flow_expire_* has
+ * removed since the last reset (nsd_flow_cpu leaves it 0).
  *
  * nsd_flow_create: slots = the power of two >= 2 * max_flows (1 <= max_flows
  * <= 2^30); all the table's device memory is allocated here, on the current
@@ -741,7 +744,8 @@ typedef struct nsd_flow {          /* 72 bytes; bytes 0..37 are the key */
 	uint64_t first, last;      /* base + index of the flow's first / last packet */
 } nsd_flow;
 enum { NSD_FLOW_ST_PKTS, NSD_FLOW_ST_KEYED, NSD_FLOW_ST_NOIP, NSD_FLOW_ST_SKIPPED,
-       NSD_FLOW_ST_FULL /* packets dropped: every slot taken */, NSD_FLOW_ST_FLOWS, NSD_FLOW_NSTATS = 8 };
+       NSD_FLOW_ST_FULL /* packets dropped: every slot taken */, NSD_FLOW_ST_FLOWS,
+       NSD_FLOW_ST_EXPIRED /* flows removed by nsd_flow_expire_*, cumulative */, NSD_FLOW_NSTATS = 8 };
 typedef struct nsd_flow_table nsd_flow_table;
 nsd_flow_table *nsd_flow_create(uint32_t max_flows);
 void nsd_flow_destroy(nsd_flow_table *t);
@@ -825,6 +829,89 @@ int  nsd_flow_conv_device(nsd_flow_table *t, int by, uint32_t k, nsd_conv *d_con
 			  uint32_t *d_count /* [2] */, void *d_workspace, void *stream);
 long nsd_flow_conversations(nsd_flow_table *t, int by, uint32_t k, nsd_conv *conv, uint64_t *stats);
 long nsd_conv_cpu(const nsd_flow *flows, size_t n, int by, nsd_conv *conv, uint32_t max);
+
+/* ---- flow expiry: idle flows leave the table as rows -------------------------
+ * flowtop's table does not fill for good: conntrack times flows out and
+ * flow_event_cb drops the entry on NFCT_T_DESTROY (flowtop.c:1612-1628); a
+ * flow exporter (NetFlow / IPFIX) does the same - a flow idle for long enough
+ * leaves as one final row and its slot is reused.  These entries do that for
+ * the flow table, so a feed that never ends, or a file with more flows than
+ * max_flows, does not end with every new flow counted in NSD_FLOW_ST_FULL.
+ *
+ * What qualifies:
+ *   A flow qualifies when its last < before; `before` is in the unit of
+ *   first / last (base + index, whatever the caller fed as base).  before = 0
+ *   expires nothing, before = UINT64_MAX every flow.
+ * Paired expiry: flags is 0 or NSD_FLOW_EXPIRE_PAIRED (any other bit:
+ *   NSD_ERR_ARG).  With the flag a flow whose reverse (src / dst and sport /
+ *   dport swapped, l3 / l4 kept: the conversations' pairing rule) is in the
+ *   table qualifies only when both directions have last < before, so a live
+ *   conversation never loses its quiet direction.  A flow without a reverse
+ *   in the table and a flow that is its own reverse follow the plain rule.
+ * The cap: at most `max` qualifying flows are removed per call, each written
+ *   as one nsd_flow row exactly as nsd_flow_export_device would have written
+ *   it; a qualifying flow that does not fit stays in the table unchanged -
+ *   nothing ever leaves the table without leaving as a row.  Which of the
+ *   qualifying flows are taken when they exceed `max` is unspecified, and only
+ *   then may a pair be split.  max = 0 counts the qualifying flows and changes
+ *   nothing.
+ * After the call every remaining flow is in the table with its key and all
+ *   five counters unchanged and is reachable by the update's probe from its
+ *   hash, and every other slot is exactly as nsd_flow_reset leaves it.  The
+ *   table is an ordinary table: update, export, conversations and reset
+ *   behave as on any table holding those flows; packets of an expired flow
+ *   that arrive later open a new flow with a new `first`, and a flow that was
+ *   dropped as FULL can enter now.
+ * stats: FLOWS becomes the remaining count, EXPIRED grows by the flows
+ *   removed; PKTS / KEYED / NOIP / SKIPPED / FULL stay cumulative.
+ *
+ * nsd_flow_expire_device: all pointers are device pointers; it only enqueues
+ * on `stream` (no allocation, no host synchronisation; a linear chain of four
+ * kernels without a memset or copy node: graph-capturable like
+ * nsd_flow_conv_device) and must be ordered on the table's stream after the
+ * last update.  d_workspace (16-byte aligned) holds
+ * nsd_flow_expire_workspace_bytes(t) = 2048 + 80 * nsd_flow_slots(t) bytes.
+ * d_count[0] = the rows written = the flows removed, d_count[1] = the flows
+ * that qualified.  Exactly d_count[0] rows are written into d_expired (8-byte
+ * aligned), never a byte past them, in unspecified order.  NSD_ERR_ARG before
+ * anything is launched: NULL table, bad flags, NULL d_expired with max > 0 or
+ * a misaligned one, NULL d_count, NULL or misaligned d_workspace.
+ * nsd_flow_expire: to host memory, synchronous, rows sorted by `first`;
+ * returns the number that qualified (the rows written are min(that, max));
+ * stats may be NULL, else the table's NSD_FLOW_NSTATS words after the call.
+ * Workspace and staging are allocated and freed inside the call, as in
+ * nsd_flow_conversations.  NSD_ERR_HIP when removed + remaining is not the
+ * flows before.
+ * nsd_flow_expire_cpu: the same rules on the host CPU over n nsd_flow rows
+ * with unique keys (nsd_flow_cpu's or nsd_flow_export's): the survivors are
+ * compacted to the front of `flows` in their input order, *remaining = their
+ * number; the first `max` qualifying rows in input order go to `expired`;
+ * returns the number that qualified.  For hosts without a GPU, and the
+ * in-product check of the rules.
+ * nsd_pcap_flows_expire: nsd_pcap_flows' loop with the records read in
+ * batches of at most `every` (1..65536).  After each batch is fed, with fed =
+ * the accepted packets so far: when fed > idle, nsd_flow_expire(t, fed - idle,
+ * flags) with room for every flow, and the removed rows, sorted by `first`, go
+ * to `sink` (never called for zero rows); a non-zero return of `sink` ends the
+ * loop and the entry returns NSD_ERR_ARG.  A record above NSD_MAX_CAPLEN ends
+ * the batch before it early and is a batch of its own, as in nsd_pcap_flows.
+ * The flows still in the table at the end of the file stay there for the
+ * caller to export.  Returns the packets fed or a negative NSD_ERR_*. */
+#define NSD_FLOW_EXPIRE_PAIRED 1u
+size_t nsd_flow_expire_workspace_bytes(const nsd_flow_table *t);
+int  nsd_flow_expire_device(nsd_flow_table *t, uint64_t before, uint32_t flags,
+			    nsd_flow *d_expired, uint32_t max, uint32_t *d_count /* [2] */,
+			    void *d_workspace, void *stream);
+long nsd_flow_expire(nsd_flow_table *t, uint64_t before, uint32_t flags,
+		     nsd_flow *expired, uint32_t max, uint64_t *stats);
+long nsd_flow_expire_cpu(nsd_flow *flows, size_t n, uint64_t before, uint32_t flags,
+			 nsd_flow *expired, uint32_t max, size_t *remaining);
+/* (behind the row type's tag: a line that begins `typedef int (` reads as a
+ * function named int to the scan of this header in tests/test_abi.py) */
+struct nsd_flow; typedef int (*nsd_flow_sink)(const nsd_flow *rows, uint32_t n, void *user);
+long nsd_pcap_flows_expire(const char *path, int mode, const struct nsd_bpf_prog *filter,
+			   nsd_flow_table *t, uint32_t every, uint64_t idle, uint32_t flags,
+			   nsd_flow_sink sink, void *user);
 
 /* Pinned host memory for the pipe's buffers. */
 void *nsd_host_alloc(size_t len);

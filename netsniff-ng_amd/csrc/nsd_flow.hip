@@ -25,6 +25,8 @@
 // A flow is in the table wholly or not at all: slots never change owner, so
 // the slots a flow's packet found taken by other flows stay so for every
 // later packet of that flow, and a packet that meets its flow's slot matches.
+// (Expiry, below, keeps this true for the update: it never empties a slot in
+// place but rebuilds the table from its survivors between two updates.)
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
@@ -369,6 +371,38 @@ __device__ __forceinline__ bool key_bytes_less(const Key &a, const Key &b)
 	return false;
 }
 
+// the reverse of a key: src / dst and sport / dport swapped, l3 / l4 kept
+__device__ __forceinline__ void reverse_key(const Key &k, Key &r)
+{
+	r.w[0] = k.w[2];
+	r.w[1] = k.w[3];
+	r.w[2] = k.w[0];
+	r.w[3] = k.w[1];
+	r.w[4] = (k.w[4] & ~0xFFFFFFFFull) | (k.w[4] & 0xFFFFu) << 16 | (k.w[4] >> 16 & 0xFFFFu);
+}
+
+// The slot that holds key r in a table whose slots are EMPTY or OCCUPIED
+// (after the commit), or NOSLOT: the update's probe, read-only.  EMPTY ends
+// it, and the slot count bounds it (a table without an empty slot).
+__device__ __forceinline__ uint32_t find_key(const Tab &t, const Key &r)
+{
+	const uint32_t mask = t.slots - 1;
+	uint32_t p = (uint32_t)key_hash(r) & mask;
+#pragma unroll 1
+	for (uint32_t probes = 0; probes < t.slots; probes++, p = (p + 1) & mask) {
+		const uint32_t v = t.state[p];
+		if (v == EMPTY)
+			break;
+		if (v != OCCUPIED)
+			continue;
+		Key o;
+		load_key(t, p, o);
+		if (key_eq(o, r))
+			return p;
+	}
+	return NOSLOT;
+}
+
 // One slot per lane, grid-stride.  The slot that owns its conversation emits
 // a candidate through a wave-aggregated cursor; the OR of the keys and of
 // their complements (which digits differ at all) is combined per thread, then
@@ -380,7 +414,6 @@ __global__ __launch_bounds__(BLOCK) void conv_pair(Tab t, ConvWs w, int by)
 		red[threadIdx.x] = 0;
 	__syncthreads();
 	const uint32_t lane = threadIdx.x & 63;
-	const uint32_t mask = t.slots - 1;
 	const uint64_t stride = (uint64_t)gridDim.x * BLOCK;
 	uint64_t o1h = 0, o1l = 0, o0h = 0, o0l = 0;
 #pragma unroll 1
@@ -393,30 +426,12 @@ __global__ __launch_bounds__(BLOCK) void conv_pair(Tab t, ConvWs w, int by)
 		if (occ) {
 			Key k, r;
 			load_key(t, (uint32_t)s, k);
-			r.w[0] = k.w[2];
-			r.w[1] = k.w[3];
-			r.w[2] = k.w[0];
-			r.w[3] = k.w[1];
-			r.w[4] = (k.w[4] & ~0xFFFFFFFFull) | (k.w[4] & 0xFFFFu) << 16 | (k.w[4] >> 16 & 0xFFFFu);
+			reverse_key(k, r);
 			const Cnt c = t.cnt[s];
 			uint64_t metric = by == NSD_CONV_BY_PKTS ? c.pkts : c.bytes;
 			own = true;
 			if (!key_eq(k, r)) {
-				uint32_t p = (uint32_t)key_hash(r) & mask;
-#pragma unroll 1
-				for (uint32_t probes = 0; probes < t.slots; probes++, p = (p + 1) & mask) {
-					const uint32_t v = t.state[p];
-					if (v == EMPTY)
-						break;
-					if (v != OCCUPIED)
-						continue;
-					Key o;
-					load_key(t, p, o);
-					if (key_eq(o, r)) {
-						rev = p;
-						break;
-					}
-				}
+				rev = find_key(t, r);
 				if (rev != NOSLOT) {
 					const Cnt d = t.cnt[rev];
 					own = c.first < d.first || (c.first == d.first && key_bytes_less(k, r));
@@ -637,6 +652,216 @@ __global__ __launch_bounds__(BLOCK) void conv_gather(Tab t, ConvWs w, uint32_t k
 		o[8] = e.bytes;
 		o[9] = c.first < e.first ? c.first : e.first;
 		o[10] = c.last > e.last ? c.last : e.last;
+	}
+}
+
+// ---- expiry -------------------------------------------------------------------
+// Idle flows leave the table as rows (the header's "flow expiry").  Emptying a
+// slot inside a probe chain would cut off every flow behind it - the next
+// update would insert such a flow a second time - so nothing is deleted in
+// place and the update / commit kernels know nothing of expiry: the table is
+// rebuilt from its survivors.  After the commit on the table's stream, state is
+// EMPTY or OCCUPIED:
+//   expire_init      zeroes the workspace header (a kernel, as conv_init);
+//   expire_split     reads the table: a qualifying flow takes a position from
+//                    the `qualified` cursor and, below `max`, leaves as a row;
+//                    every other flow copies its key and counters into the
+//                    workspace through the `survivors` cursor;
+//   expire_clear     nothing removed: returns, the table is not written at
+//                    all.  Else every slot becomes what flow_reset makes it;
+//   expire_reinsert  one survivor per lane claims the first EMPTY slot of its
+//                    probe with one CAS EMPTY -> OCCUPIED and stores its rows.
+// The flows removed are min(qualified, max): the positions below `max`.
+//
+// Workspace: an EXP_HDR-byte header, then the survivors' rows, 80 bytes each:
+// the five key words, then the Cnt.  The kernels bound the counts they read
+// from the header by `slots`.
+constexpr size_t EXP_HDR = 2048;
+
+struct ExpHdr {
+	uint32_t qualified;   // expire_split's cursor of qualifying flows
+	uint32_t survivors;   // ... and of the flows that stay
+	uint32_t lost;        // survivors that found no slot (cannot happen; the host entry checks)
+	uint32_t pad;
+};
+static_assert(sizeof(ExpHdr) <= EXP_HDR, "expire header");
+
+struct ExpWs {
+	ExpHdr *h;
+	uint64_t *rows;   // 10 words per survivor
+	uint32_t slots;
+};
+
+__global__ __launch_bounds__(BLOCK) void expire_init(ExpWs w)
+{
+	for (uint32_t i = threadIdx.x; i < EXP_HDR / 4; i += BLOCK)
+		((uint32_t *)w.h)[i] = 0;
+}
+
+__device__ __forceinline__ uint32_t expire_removed(const ExpWs &w, uint32_t max)
+{
+	uint32_t n = w.h->qualified;
+	n = n < w.slots ? n : w.slots;
+	return n < max ? n : max;
+}
+__device__ __forceinline__ uint32_t expire_survivors(const ExpWs &w)
+{
+	const uint32_t n = w.h->survivors;
+	return n < w.slots ? n : w.slots;
+}
+
+// a position for every lane of `m` from one atomic per wave (flow_export's cursor)
+__device__ __forceinline__ uint64_t wave_cursor(uint32_t *cursor, uint64_t m, uint32_t lane)
+{
+	uint32_t at = 0;
+	if (lane == 0)
+		at = __hip_atomic_fetch_add(cursor, (uint32_t)__popcll(m), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+	at = __shfl(at, 0, 64);
+	return (uint64_t)at + (uint32_t)__popcll(m & ((1ull << lane) - 1));
+}
+
+// One slot per lane, grid-stride; only reads the table.
+__global__ __launch_bounds__(BLOCK) void expire_split(Tab t, ExpWs w, uint64_t before, uint32_t flags, uint64_t *out,
+						      uint32_t max)
+{
+	const uint32_t lane = threadIdx.x & 63;
+	const uint64_t stride = (uint64_t)gridDim.x * BLOCK;
+#pragma unroll 1
+	for (uint64_t s0 = (uint64_t)blockIdx.x * BLOCK + (threadIdx.x & ~63u); s0 < t.slots; s0 += stride) {
+		const uint64_t s = s0 + lane;
+		const bool occ = s < t.slots && t.state[s] == OCCUPIED;
+		if (!__ballot(occ))
+			continue;
+		Key k;
+		Cnt c;
+		bool idle = false;
+		if (occ) {
+			load_key(t, (uint32_t)s, k);
+			c = t.cnt[s];
+			idle = c.last < before;
+			if (idle && (flags & NSD_FLOW_EXPIRE_PAIRED)) {
+				Key r;
+				reverse_key(k, r);
+				if (!key_eq(k, r)) {
+					const uint32_t rev = find_key(t, r);
+					if (rev != NOSLOT)
+						idle = t.cnt[rev].last < before;
+				}
+			}
+		}
+		const uint64_t mq = __ballot(idle);
+		bool stay = occ && !idle;
+		if (mq) {
+			const uint64_t pos = wave_cursor(&w.h->qualified, mq, lane);
+			if (idle) {
+				if (pos < max) {
+					uint64_t *o = out + 9ull * pos;
+					o[0] = k.w[0];
+					o[1] = k.w[1];
+					o[2] = k.w[2];
+					o[3] = k.w[3];
+					o[4] = k.w[4] | (uint64_t)(c.flags & 0xFFu) << 48;
+					o[5] = c.pkts;
+					o[6] = c.bytes;
+					o[7] = c.first;
+					o[8] = c.last;
+				} else {
+					stay = true;   // no room for its row: it stays as it is
+				}
+			}
+		}
+		const uint64_t ms = __ballot(stay);
+		if (!ms)
+			continue;
+		const uint64_t pos = wave_cursor(&w.h->survivors, ms, lane);
+		// (max = 0 removes nothing: the rows would not be read)
+		if (stay && max && pos < t.slots) {
+			uint64_t *o = w.rows + 10ull * pos;
+			o[0] = k.w[0];
+			o[1] = k.w[1];
+			o[2] = k.w[2];
+			o[3] = k.w[3];
+			o[4] = k.w[4];
+			o[5] = c.pkts;
+			o[6] = c.bytes;
+			o[7] = c.first;
+			o[8] = c.last;
+			o[9] = c.flags;
+		}
+	}
+}
+
+// count[0] = the flows removed, count[1] = those that qualified.  Nothing
+// removed: the table stays as it is.  Else every slot as flow_reset leaves it;
+// the stats stay but for FLOWS and EXPIRED.
+__global__ __launch_bounds__(BLOCK) void expire_clear(Tab t, ExpWs w, uint32_t max, uint32_t *count)
+{
+	const uint32_t removed = expire_removed(w, max);
+	if (blockIdx.x == 0 && threadIdx.x == 0) {
+		count[0] = removed;
+		count[1] = w.h->qualified;
+		if (removed) {
+			t.stats[NSD_FLOW_ST_FLOWS] -= removed;
+			t.stats[NSD_FLOW_ST_EXPIRED] += removed;
+		}
+	}
+	if (!removed)
+		return;
+	const uint64_t stride = (uint64_t)gridDim.x * BLOCK;
+	for (uint64_t s = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; s < t.slots; s += stride) {
+		t.state[s] = EMPTY;
+		Cnt c;
+		c.pkts = c.bytes = c.last = 0;
+		c.first = UINT64_MAX;
+		c.flags = c.pad = 0;
+		t.cnt[s] = c;
+	}
+}
+
+// One survivor per lane, grid-stride.  Keys are unique, so a lane never
+// compares against a slot: it takes the first EMPTY one of its probe (one
+// relaxed CAS; a slot another lane took is passed by) and stores its own rows
+// there with plain stores, which nobody reads before the next kernel.
+__global__ __launch_bounds__(BLOCK) void expire_reinsert(Tab t, ExpWs w, uint32_t max)
+{
+	if (!expire_removed(w, max))
+		return;
+	const uint32_t n = expire_survivors(w);
+	const uint32_t mask = t.slots - 1;
+	const uint64_t stride = (uint64_t)gridDim.x * BLOCK;
+#pragma unroll 1
+	for (uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; i < n; i += stride) {
+		const uint64_t *r = w.rows + 10ull * i;
+		Key k;
+		for (int j = 0; j < 5; j++)
+			k.w[j] = r[j];
+		uint32_t s = (uint32_t)key_hash(k) & mask, slot = NOSLOT;
+#pragma unroll 1
+		for (uint32_t probes = 0; probes < t.slots; probes++, s = (s + 1) & mask) {
+			if (__hip_atomic_load(&t.state[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != EMPTY)
+				continue;
+			uint32_t expect = EMPTY;
+			if (__hip_atomic_compare_exchange_strong(&t.state[s], &expect, OCCUPIED, __ATOMIC_RELAXED,
+								 __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
+				slot = s;
+				break;
+			}
+		}
+		if (slot == NOSLOT) {
+			add_rlx(&w.h->lost, 1u);
+			continue;
+		}
+		uint64_t *kp = t.key + 5ull * slot;
+		for (int j = 0; j < 5; j++)
+			kp[j] = k.w[j];
+		Cnt c;
+		c.pkts = r[5];
+		c.bytes = r[6];
+		c.first = r[7];
+		c.last = r[8];
+		c.flags = (uint32_t)r[9];
+		c.pad = 0;
+		t.cnt[slot] = c;
 	}
 }
 
@@ -911,6 +1136,85 @@ extern "C" long nsd_flow_conversations(nsd_flow_table *t, int by, uint32_t k, ns
 	return (long)count[1];
 }
 
+// ---- expiry: the entries ------------------------------------------------------
+extern "C" size_t nsd_flow_expire_workspace_bytes(const nsd_flow_table *t)
+{
+	return t ? EXP_HDR + 80 * (size_t)t->tab.slots : 0;
+}
+
+// init | split | clear | reinsert: a linear chain of kernels on `stream`
+extern "C" int nsd_flow_expire_device(nsd_flow_table *t, uint64_t before, uint32_t flags, nsd_flow *d_expired,
+				      uint32_t max, uint32_t *d_count, void *d_workspace, void *stream)
+{
+	if (!t || (flags & ~NSD_FLOW_EXPIRE_PAIRED) || !d_count || !d_workspace || (max && !d_expired) ||
+	    ((uintptr_t)d_expired & 7) || ((uintptr_t)d_workspace & 15) || ((uintptr_t)d_count & 3))
+		return NSD_ERR_ARG;
+	hipStream_t s = (hipStream_t)stream;
+	uint8_t *m = (uint8_t *)d_workspace;
+	const ExpWs w{ (ExpHdr *)m, (uint64_t *)(m + EXP_HDR), t->tab.slots };
+	const dim3 grid(grid_for(t, t->tab.slots)), block(BLOCK);
+	hipLaunchKernelGGL(expire_init, dim3(1), block, 0, s, w);
+	hipLaunchKernelGGL(expire_split, grid, block, 0, s, t->tab, w, before, flags, (uint64_t *)d_expired, max);
+	hipLaunchKernelGGL(expire_clear, grid, block, 0, s, t->tab, w, max, d_count);
+	hipLaunchKernelGGL(expire_reinsert, grid, block, 0, s, t->tab, w, max);
+	t->last = s;
+	return hip_ok(hipGetLastError(), "launch") ? NSD_OK : NSD_ERR_HIP;
+}
+
+long nsd_flow_expire_rows(nsd_flow_table *t, uint64_t before, uint32_t flags, uint32_t max,
+			  std::vector<nsd_flow> &rows, uint64_t *stats)
+{
+	rows.clear();
+	if (!t || (flags & ~NSD_FLOW_EXPIRE_PAIRED))
+		return NSD_ERR_ARG;
+	hipStream_t s = t->last;
+	uint64_t st[NSD_FLOW_NSTATS];
+	if (!hip_ok(hipMemcpyAsync(st, t->tab.stats, sizeof(st), hipMemcpyDeviceToHost, s), "D2H") ||
+	    !hip_ok(hipStreamSynchronize(s), "sync"))
+		return NSD_ERR_HIP;
+	// (no more rows than flows)
+	const uint32_t have = (uint32_t)st[NSD_FLOW_ST_FLOWS], want = max < have ? max : have;
+	const size_t o_rows = 256, o_ws = (o_rows + (size_t)want * sizeof(nsd_flow) + 255) & ~(size_t)255;
+	uint8_t *d = nullptr;
+	if (!hip_ok(hipMalloc(&d, o_ws + nsd_flow_expire_workspace_bytes(t)), "hipMalloc"))
+		return NSD_ERR_NOMEM;
+	uint32_t *d_count = (uint32_t *)d;
+	nsd_flow *d_rows = (nsd_flow *)(d + o_rows);
+	uint32_t count[2] = { 0, 0 };
+	ExpHdr h{};
+	bool ok = nsd_flow_expire_device(t, before, flags, d_rows, want, d_count, d + o_ws, s) == NSD_OK &&
+		  hip_ok(hipMemcpyAsync(count, d_count, 8, hipMemcpyDeviceToHost, s), "D2H") &&
+		  hip_ok(hipMemcpyAsync(&h, d + o_ws, sizeof(h), hipMemcpyDeviceToHost, s), "D2H") &&
+		  hip_ok(hipMemcpyAsync(st, t->tab.stats, sizeof(st), hipMemcpyDeviceToHost, s), "D2H") &&
+		  hip_ok(hipStreamSynchronize(s), "sync") && count[0] <= want;
+	if (ok && count[0]) {
+		rows.resize(count[0]);
+		ok = hip_ok(hipMemcpy(rows.data(), d_rows, (size_t)count[0] * sizeof(nsd_flow), hipMemcpyDeviceToHost), "D2H");
+	}
+	(void)hipFree(d);
+	// every flow of before either left as a row or is back in the table
+	if (!ok || h.lost || (uint64_t)count[0] + h.survivors != have || st[NSD_FLOW_ST_FLOWS] != h.survivors) {
+		rows.clear();
+		return NSD_ERR_HIP;
+	}
+	sort_by_first(rows);
+	if (stats)
+		memcpy(stats, st, sizeof(st));
+	return (long)count[1];
+}
+
+extern "C" long nsd_flow_expire(nsd_flow_table *t, uint64_t before, uint32_t flags, nsd_flow *expired, uint32_t max,
+				uint64_t *stats)
+{
+	if (max && !expired)
+		return NSD_ERR_ARG;
+	std::vector<nsd_flow> rows;
+	const long q = nsd_flow_expire_rows(t, before, flags, max, rows, stats);
+	if (q >= 0 && !rows.empty())
+		memcpy(expired, rows.data(), rows.size() * sizeof(nsd_flow));
+	return q;
+}
+
 // ---- the same aggregation on the host -----------------------------------
 namespace {
 struct KeyHash {
@@ -1017,6 +1321,55 @@ extern "C" long nsd_conv_cpu(const nsd_flow *flows, size_t n, int by, nsd_conv *
 	if (k)
 		memcpy(conv, rows.data(), k * sizeof(nsd_conv));
 	return (long)rows.size();
+}
+
+// The expiry rules on the host over flow rows (unique keys, any order): a hash
+// map from key to row for the reverse lookup.  Survivors keep their input
+// order at the front of `flows`; the first `max` qualifying rows in input
+// order go to `expired`, the others stay.
+extern "C" long nsd_flow_expire_cpu(nsd_flow *flows, size_t n, uint64_t before, uint32_t flags, nsd_flow *expired,
+				    uint32_t max, size_t *remaining)
+{
+	if ((flags & ~NSD_FLOW_EXPIRE_PAIRED) || (n && !flows) || (max && !expired) || !remaining)
+		return NSD_ERR_ARG;
+	auto key_of = [](const nsd_flow &f) {
+		Key k;
+		memcpy(k.w, &f, 40);
+		k.w[4] &= 0x0000FFFFFFFFFFFFull;   // tcp_flags, rsvd
+		return k;
+	};
+	std::unordered_map<Key, size_t, KeyHash, KeyEq> map;
+	if (flags & NSD_FLOW_EXPIRE_PAIRED) {
+		map.reserve(n);
+		for (size_t i = 0; i < n; i++)
+			map.emplace(key_of(flows[i]), i);
+	}
+	// decided over the rows as given, before any of them moves
+	std::vector<uint8_t> idle(n);
+	for (size_t i = 0; i < n; i++) {
+		const nsd_flow &f = flows[i];
+		idle[i] = f.last < before;
+		if (!idle[i] || !(flags & NSD_FLOW_EXPIRE_PAIRED))
+			continue;
+		nsd_flow r = f;
+		memcpy(r.src, f.dst, 16);
+		memcpy(r.dst, f.src, 16);
+		r.sport = f.dport;
+		r.dport = f.sport;
+		const Key k = key_of(f), kr = key_of(r);
+		const auto it = key_eq(k, kr) ? map.end() : map.find(kr);
+		if (it != map.end())
+			idle[i] = flows[it->second].last < before;
+	}
+	size_t qualified = 0, kept = 0;
+	for (size_t i = 0; i < n; i++) {
+		if (idle[i] && qualified++ < max)
+			expired[qualified - 1] = flows[i];
+		else
+			flows[kept++] = flows[i];
+	}
+	*remaining = kept;
+	return (long)qualified;
 }
 
 // ---- host-memory entries --------------------------------------------------

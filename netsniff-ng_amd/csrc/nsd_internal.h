@@ -14,6 +14,7 @@
 #include <stdio.h>
 
 #include <string>
+#include <vector>
 
 #include "../../include/netsniff_dissect.h"
 
@@ -88,6 +89,10 @@ extern "C" NSD_HIDDEN long nsd_flow_feed_host(nsd_flow_table *t, const uint8_t *
 extern "C" NSD_HIDDEN int nsd_flow_feed_records(nsd_flow_table *t, const uint8_t *frames, size_t frames_len,
 						const nsd_desc_t *desc, uint32_t n, const nsd_rec *rec,
 						const uint32_t *ext, uint32_t ext_words, uint64_t base);
+// nsd_flow_expire with room for every flow: the removed rows, sorted by
+// `first`, into `rows` (nsd_flow.hip; the capture-file loop's, nsd_replay.cpp)
+NSD_HIDDEN long nsd_flow_expire_rows(nsd_flow_table *t, uint64_t before, uint32_t flags, uint32_t max,
+				     std::vector<nsd_flow> &rows, uint64_t *stats);
 
 // what dissector_cleanup_all (nsd_proto.cpp) lets go of: the interface name
 // cache (nsd_format.cpp; each replay resets it too), the replay's cached

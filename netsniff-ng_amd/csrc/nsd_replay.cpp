@@ -98,9 +98,17 @@ long read_big(nsd_pcap *p, const nsd_bpf_prog *filter, std::vector<uint8_t> &fra
 // batches of the reader go through the device filter / walk / update; a
 // record no batch carries is filtered and walked by the per-packet path over
 // its first NSD_MAX_CAPLEN bytes and added with its whole caplen.
-extern "C" long nsd_pcap_flows(const char *path, int mode, const nsd_bpf_prog *filter, nsd_flow_table *t)
+// Batches carry at most `every` records; after each one fed (a record no
+// batch carries is a batch of its own) `after(fed)` runs when given, and a
+// negative return of it ends the loop with that status.
+namespace {
+constexpr uint32_t FLOWS_MAX_N = 1u << 16;
+
+template <class After>
+long pcap_flows_loop(const char *path, int mode, const nsd_bpf_prog *filter, nsd_flow_table *t, uint32_t every,
+		     After after)
 {
-	if (!path || !t || mode < PRINT_NORM || mode > PRINT_NONE)
+	if (!path || !t || mode < PRINT_NORM || mode > PRINT_NONE || every == 0 || every > FLOWS_MAX_N)
 		return NSD_ERR_ARG;
 	nsd_pcap *p = nsd_pcap_open(path);
 	if (!p)
@@ -108,14 +116,13 @@ extern "C" long nsd_pcap_flows(const char *path, int mode, const nsd_bpf_prog *f
 	const int lt = (int)p->linktype;
 	const bool ll_used = has_ll(p);
 	constexpr size_t CAP = 16u << 20;
-	constexpr uint32_t MAX_N = 1u << 16;
 	std::vector<uint8_t> frames(CAP), big;
-	std::vector<nsd_desc_t> desc(MAX_N);
-	std::vector<nsd_sll_t> sll(MAX_N);
+	std::vector<nsd_desc_t> desc(every);
+	std::vector<nsd_sll_t> sll(every);
 	uint64_t fed = 0;
 	long rc = NSD_OK;
 	while (rc == NSD_OK) {
-		const long n = read_batch(p, frames.data(), CAP, desc.data(), sll.data(), nullptr, MAX_N, nullptr, nullptr,
+		const long n = read_batch(p, frames.data(), CAP, desc.data(), sll.data(), nullptr, every, nullptr, nullptr,
 					  nullptr);
 		if (n == 0)
 			break;
@@ -126,6 +133,8 @@ extern "C" long nsd_pcap_flows(const char *path, int mode, const nsd_bpf_prog *f
 				rc = k;
 			else
 				fed += (uint64_t)k;
+			if (rc == NSD_OK)
+				rc = after(fed);
 			continue;
 		}
 		if (n != NSD_ERR_CAPLEN) {
@@ -150,10 +159,37 @@ extern "C" long nsd_pcap_flows(const char *path, int mode, const nsd_bpf_prog *f
 		if (rc == NSD_OK)
 			rc = nsd_flow_feed_records(t, big.data(), head, &d, 1, &rec, ext, NSD_EXT_WORDS(NSD_EXT_MAX_LAYERS), fed);
 		if (rc == NSD_OK)
-			fed++;
+			rc = after(++fed);
 	}
 	nsd_pcap_close(p);
 	return rc == NSD_OK ? (long)fed : rc;
+}
+} // namespace
+
+extern "C" long nsd_pcap_flows(const char *path, int mode, const nsd_bpf_prog *filter, nsd_flow_table *t)
+{
+	return pcap_flows_loop(path, mode, filter, t, FLOWS_MAX_N, [](uint64_t) { return (long)NSD_OK; });
+}
+
+// The same loop with idle flows leaving between the batches (the header's
+// "flow expiry"): once more than `idle` packets are fed, the flows whose last
+// packet lies more than `idle` packets back go to `sink`, sorted by `first`.
+extern "C" long nsd_pcap_flows_expire(const char *path, int mode, const nsd_bpf_prog *filter, nsd_flow_table *t,
+				      uint32_t every, uint64_t idle, uint32_t flags, nsd_flow_sink sink, void *user)
+{
+	if (!sink || (flags & ~NSD_FLOW_EXPIRE_PAIRED))
+		return NSD_ERR_ARG;
+	std::vector<nsd_flow> rows;
+	return pcap_flows_loop(path, mode, filter, t, every, [&](uint64_t fed) -> long {
+		if (fed <= idle)
+			return NSD_OK;
+		const long q = nsd_flow_expire_rows(t, fed - idle, flags, UINT32_MAX, rows, nullptr);
+		if (q < 0)
+			return q;
+		if (!rows.empty() && sink(rows.data(), (uint32_t)rows.size(), user) != 0)
+			return NSD_ERR_ARG;
+		return NSD_OK;
+	});
 }
 
 // The replay's staging: pinned host buffers per batch slot and the device pipe.

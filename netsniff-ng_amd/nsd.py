@@ -129,7 +129,9 @@ ABI_SYMBOLS = ["dissector_init_all", "dissector_entry_point", "dissector_cleanup
                "nsd_set_record_ring", "nsd_set_debug_fill", "nsd_flow_create", "nsd_flow_destroy",
                "nsd_flow_slots", "nsd_flow_reset", "nsd_flow_update_device", "nsd_flow_export_device",
                "nsd_flow_export", "nsd_flow_batch", "nsd_pcap_flows", "nsd_flow_cpu",
-               "nsd_flow_conv_workspace_bytes", "nsd_flow_conv_device", "nsd_flow_conversations", "nsd_conv_cpu"]
+               "nsd_flow_conv_workspace_bytes", "nsd_flow_conv_device", "nsd_flow_conversations", "nsd_conv_cpu",
+               "nsd_flow_expire_workspace_bytes", "nsd_flow_expire_device", "nsd_flow_expire", "nsd_flow_expire_cpu",
+               "nsd_pcap_flows_expire"]
 
 # struct sockaddr_ll (nsd_sll_t), one per packet for LINKTYPE_LINUX_SLL batches
 SLL_DTYPE = np.dtype([("family", "<u2"), ("protocol", ">u2"), ("ifindex", "<i4"), ("hatype", "<u2"),
@@ -147,7 +149,10 @@ FLOW_DTYPE = np.dtype([("src", "u1", (16,)), ("dst", "u1", (16,)), ("sport", "<u
                        ("bytes", "<u8"), ("first", "<u8"), ("last", "<u8")])
 FLOW_BYTES = 72
 FLOW_NSTATS = 8
-FLOW_ST_PKTS, FLOW_ST_KEYED, FLOW_ST_NOIP, FLOW_ST_SKIPPED, FLOW_ST_FULL, FLOW_ST_FLOWS = range(6)
+FLOW_ST_PKTS, FLOW_ST_KEYED, FLOW_ST_NOIP, FLOW_ST_SKIPPED, FLOW_ST_FULL, FLOW_ST_FLOWS, FLOW_ST_EXPIRED = range(7)
+FLOW_EXPIRE_PAIRED = 1
+# nsd_flow_sink: the callback nsd_pcap_flows_expire hands each expiry's rows to
+FLOW_SINK = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p)
 
 # nsd_conv: one conversation (bytes 0..37 are the originator's flow key)
 CONV_DTYPE = np.dtype([("src", "u1", (16,)), ("dst", "u1", (16,)), ("sport", "<u2"), ("dport", "<u2"),
@@ -297,6 +302,12 @@ def lib():
                 ("nsd_flow_conv_device", _int, [_vp, _int, _u32, _vp, _vp, _vp, _vp]),
                 ("nsd_flow_conversations", ctypes.c_long, [_vp, _int, _u32, _vp, _vp]),
                 ("nsd_conv_cpu", ctypes.c_long, [_vp, _sz, _int, _vp, _u32]),
+                ("nsd_flow_expire_workspace_bytes", _sz, [_vp]),
+                ("nsd_flow_expire_device", _int, [_vp, _u64, _u32, _vp, _u32, _vp, _vp, _vp]),
+                ("nsd_flow_expire", ctypes.c_long, [_vp, _u64, _u32, _vp, _u32, _vp]),
+                ("nsd_flow_expire_cpu", ctypes.c_long, [_vp, _sz, _u64, _u32, _vp, _u32, _vp]),
+                ("nsd_pcap_flows_expire", ctypes.c_long,
+                 [ctypes.c_char_p, _int, _vp, _vp, _u32, _u64, _u32, FLOW_SINK, _vp]),
                 ("nsd_last_schedule", _int, [])):
             if hasattr(L, name):
                 getattr(L, name).restype = res
@@ -831,6 +842,39 @@ class FlowTable:
         _check(0 if n >= 0 else n, "nsd_flow_conversations")
         return conv[:min(n, cap)], stats
 
+    def expire_device(self, before, flags=0, max_flows=None, flows=None, count=None, workspace=None, stream=None):
+        """The flows with last < before leave the table as rows
+        (nsd_flow_expire_device; flags = FLOW_EXPIRE_PAIRED: a conversation
+        leaves only when both directions are idle): (flows u8[max*72], count
+        i32[2] = rows written = flows removed, flows that qualified) cuda
+        tensors; row order unspecified.  max_flows = None: room for all."""
+        import torch
+        if flows is None:
+            flows = torch.empty((self.slots if max_flows is None else max_flows) * FLOW_BYTES, dtype=torch.uint8,
+                                device="cuda")
+        if max_flows is None:
+            max_flows = flows.numel() // FLOW_BYTES
+        if count is None:
+            count = torch.zeros(2, dtype=torch.int32, device=flows.device)
+        if workspace is None:
+            workspace = torch.empty(self.L.nsd_flow_expire_workspace_bytes(self.h), dtype=torch.uint8,
+                                    device=flows.device)
+        rc = self.L.nsd_flow_expire_device(self.h, before, flags, flows.data_ptr(), max_flows, count.data_ptr(),
+                                           workspace.data_ptr(), self._stream(stream, flows.device))
+        _check(rc, "nsd_flow_expire_device")
+        return flows, count
+
+    def expire(self, before, flags=0, max_flows=None):
+        """(removed flows FLOW_DTYPE sorted by `first`, the number that
+        qualified, stats u64[8] after the call) in host memory
+        (nsd_flow_expire); synchronous."""
+        cap = self.slots if max_flows is None else max_flows
+        flows = np.zeros(max(cap, 1), dtype=FLOW_DTYPE)
+        stats = np.zeros(FLOW_NSTATS, dtype=np.uint64)
+        n = self.L.nsd_flow_expire(self.h, before, flags, flows.ctypes.data, cap, stats.ctypes.data)
+        _check(0 if n >= 0 else n, "nsd_flow_expire")
+        return flows[:min(n, cap)], n, stats
+
     def close(self):
         if getattr(self, "h", None):
             self.L.nsd_flow_destroy(self.h)
@@ -890,6 +934,42 @@ def pcap_flows(path, table, mode=PRINT_NORM, prog=None):
     n = lib().nsd_pcap_flows(os.fsencode(path), mode, prog.h if prog is not None else None, table.h)
     _check(0 if n >= 0 else n, "nsd_pcap_flows")
     return n
+
+
+def flow_expire_cpu(flows, before, flags=0, max_flows=None):
+    """The expiry rules on the host CPU (nsd_flow_expire_cpu) over flow rows
+    (FLOW_DTYPE, unique keys): (remaining rows in their input order, expired
+    rows = the first max_flows qualifying ones in input order, the number
+    that qualified)."""
+    rest = np.array(flows, dtype=FLOW_DTYPE, ndmin=1)     # (a copy: the call compacts it)
+    cap = len(rest) if max_flows is None else max_flows
+    expired = np.zeros(max(cap, 1), dtype=FLOW_DTYPE)
+    remaining = ctypes.c_size_t(0)
+    n = lib().nsd_flow_expire_cpu(rest.ctypes.data, len(rest), before, flags, expired.ctypes.data, cap,
+                                  ctypes.byref(remaining))
+    _check(0 if n >= 0 else n, "nsd_flow_expire_cpu")
+    return rest[:remaining.value], expired[:min(n, cap)], n
+
+
+def pcap_flows_expire(path, table, every, idle, flags=0, mode=PRINT_NORM, prog=None):
+    """nsd_pcap_flows with idle flows leaving between the batches
+    (nsd_pcap_flows_expire): records in batches of at most `every`; once more
+    than `idle` packets are fed, the flows whose last packet lies more than
+    `idle` packets back leave.  Returns (packets fed, [FLOW_DTYPE rows of each
+    expiry that removed any, sorted by `first`]); the flows still in the table
+    stay there for table.export()."""
+    calls = []
+
+    @FLOW_SINK
+    def sink(rows, n, user):
+        buf = ctypes.string_at(rows, n * FLOW_BYTES)
+        calls.append(np.frombuffer(buf, dtype=FLOW_DTYPE).copy())
+        return 0
+
+    n = lib().nsd_pcap_flows_expire(os.fsencode(path), mode, prog.h if prog is not None else None, table.h, every, idle,
+                                    flags, sink, None)
+    _check(0 if n >= 0 else n, "nsd_pcap_flows_expire")
+    return n, calls
 
 
 # ---- pcap replay front end (nsd_pcap.cpp the reader, nsd_replay.cpp the replay) ---------------------------------------
