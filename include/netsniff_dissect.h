@@ -913,6 +913,111 @@ long nsd_pcap_flows_expire(const char *path, int mode, const struct nsd_bpf_prog
 			   nsd_flow_table *t, uint32_t every, uint64_t idle, uint32_t flags,
 			   nsd_flow_sink sink, void *user);
 
+/* ---- flow times: capture timestamps in the flow table ------------------------
+ * flowtop keeps when a flow began and ended (struct flow_entry's
+ * timestamp_start / timestamp_stop, flowtop.c:87, filled at :653-654 and
+ * printed at :1050) and derives its rates from elapsed time
+ * (flow_entry_calc_rate, flowtop.c:387-393); conntrack times flows out after
+ * seconds, and a NetFlow / IPFIX exporter puts flowStart / flowEnd on every
+ * row and expires on an idle timeout.  first / last above are packet indices;
+ * a timed table also keeps, per flow, the smallest and the largest capture
+ * timestamp of its packets, hands them out with the rows and expires by them.
+ * Timed tables are opt-in: a table of nsd_flow_create is laid out, costs and
+ * behaves as before.
+ *
+ * Timestamps are opaque u64 values in one unit of the caller's choice and of
+ * any epoch - nanoseconds by convention, what nsd_pcap_read_batch gives as
+ * ts_ns.  0 and UINT64_MAX are legal values.
+ *   t_first = the minimum, t_last = the maximum over the flow's counted
+ *   packets.  They are a minimum and a maximum, not "the time of the packet
+ *   with the smallest index": capture files are not always monotonic (several
+ *   queues merged, a clock stepped), and the result depends neither on the
+ *   order of the packets within a batch nor on the order of the batches.  A
+ *   packet that is not counted (NSD_FLOW_ST_FULL, _NOIP, _SKIPPED) gives no
+ *   time.  A slot without a flow holds t_first = UINT64_MAX, t_last = 0.
+ * A rate is the caller's division: bytes / (t_last - t_first) of a row; there
+ * are no orders by rate or duration.
+ *
+ * nsd_flow_create_timed: as nsd_flow_create, plus 16 bytes per slot for the
+ * two times.  nsd_flow_is_timed: 1 for such a table, else 0 (NULL: 0).
+ * nsd_flow_update_device_ts: nsd_flow_update_device with d_ts[n] (u64, 8-byte
+ * aligned), packet i's timestamp; the same launch discipline (it only
+ * enqueues, two kernels, graph-capturable).  A timed table takes only this
+ * update and a plain table only the plain one: the other is NSD_ERR_ARG before
+ * anything is launched, as are a NULL or misaligned d_ts with n > 0.
+ * nsd_flowt (88 bytes) is an nsd_flow followed by t_first / t_last, nsd_convt
+ * (104 bytes) an nsd_conv followed by the minimum t_first and the maximum
+ * t_last of both directions.  nsd_flow_export_device_ts / nsd_flow_export_ts /
+ * nsd_flow_conv_device_ts / nsd_flow_conversations_ts follow their
+ * counterparts' contracts with these rows (pairing, originator, orders,
+ * selection and workspace unchanged; the host forms sort the same way).
+ * nsd_flow_expire_device_ts / nsd_flow_expire_ts: "flow expiry" above with
+ * the criterion t_last < before_ns (PAIRED: the reverse's t_last) and nsd_flowt
+ * rows; the cap, max = 0, the rebuilt table and the four-kernel chain are the
+ * same, and every remaining flow keeps its two times.
+ * nsd_flow_expire_workspace_bytes(t) = 2048 + 96 * nsd_flow_slots(t) for a
+ * timed table (both criteria: the survivors carry their times).
+ * The entries without _ts work on a timed table and give the same rows
+ * without the times (nsd_flow_expire* by `last`).  Every _ts entry on a plain
+ * table is NSD_ERR_ARG.
+ * nsd_flow_cpu_ts / nsd_conv_cpu_ts / nsd_flow_expire_cpu_ts: the host forms,
+ * over ts[n] and nsd_flowt rows.
+ * nsd_pcap_flows into a timed table feeds each accepted record's timestamp
+ * (sec * 1e9 + usec * 1000, or the ns field of the nsec / Borkmann magics).
+ * nsd_pcap_flows_expire_ts: nsd_pcap_flows_expire by time.  After each batch,
+ * now = the largest timestamp among the packets fed so far; when now >
+ * idle_ns, nsd_flow_expire_ts(t, now - idle_ns, flags) with room for every
+ * flow, the removed rows, sorted by `first`, to `sink` (never called for zero
+ * rows; a non-zero return ends the loop with NSD_ERR_ARG). */
+typedef struct nsd_flowt {         /* 88 bytes: nsd_flow, then the times */
+	uint8_t  src[16], dst[16];
+	uint16_t sport, dport;
+	uint8_t  l3, l4;
+	uint8_t  tcp_flags;
+	uint8_t  rsvd;
+	uint64_t pkts, bytes;
+	uint64_t first, last;
+	uint64_t t_first, t_last;  /* min / max timestamp of the flow's packets */
+} nsd_flowt;
+typedef struct nsd_convt {         /* 104 bytes: nsd_conv, then the times */
+	uint8_t  src[16], dst[16];
+	uint16_t sport, dport;
+	uint8_t  l3, l4;
+	uint8_t  tcp_flags_src;
+	uint8_t  tcp_flags_dst;
+	uint64_t pkts_src, bytes_src;
+	uint64_t pkts_dst, bytes_dst;
+	uint64_t first, last;
+	uint64_t t_first, t_last;  /* min t_first / max t_last over both directions */
+} nsd_convt;
+nsd_flow_table *nsd_flow_create_timed(uint32_t max_flows);
+int  nsd_flow_is_timed(const nsd_flow_table *t);
+int  nsd_flow_update_device_ts(nsd_flow_table *t, const uint8_t *d_frames, const nsd_desc_t *d_desc,
+			       uint32_t n, const nsd_rec *d_rec, const uint32_t *d_ext, uint32_t ext_words,
+			       const uint64_t *d_ts, uint64_t base, void *stream);
+int  nsd_flow_export_device_ts(nsd_flow_table *t, nsd_flowt *d_flows, uint32_t max, uint32_t *d_count,
+			       uint64_t *d_stats, void *stream);
+long nsd_flow_export_ts(nsd_flow_table *t, nsd_flowt *flows, uint32_t max, uint64_t *stats);
+int  nsd_flow_conv_device_ts(nsd_flow_table *t, int by, uint32_t k, nsd_convt *d_conv,
+			     uint32_t *d_count /* [2] */, void *d_workspace, void *stream);
+long nsd_flow_conversations_ts(nsd_flow_table *t, int by, uint32_t k, nsd_convt *conv, uint64_t *stats);
+int  nsd_flow_expire_device_ts(nsd_flow_table *t, uint64_t before_ns, uint32_t flags,
+			       nsd_flowt *d_expired, uint32_t max, uint32_t *d_count /* [2] */,
+			       void *d_workspace, void *stream);
+long nsd_flow_expire_ts(nsd_flow_table *t, uint64_t before_ns, uint32_t flags,
+			nsd_flowt *expired, uint32_t max, uint64_t *stats);
+long nsd_flow_cpu_ts(const uint8_t *frames, const nsd_desc_t *desc, uint32_t n, const nsd_rec *rec,
+		     const uint32_t *ext, const uint64_t *ts, uint64_t base, nsd_flowt *flows, uint32_t max,
+		     uint64_t *stats);
+long nsd_conv_cpu_ts(const nsd_flowt *flows, size_t n, int by, nsd_convt *conv, uint32_t max);
+long nsd_flow_expire_cpu_ts(nsd_flowt *flows, size_t n, uint64_t before_ns, uint32_t flags,
+			    nsd_flowt *expired, uint32_t max, size_t *remaining);
+/* (behind the row type's tag, as nsd_flow_sink above) */
+struct nsd_flowt; typedef int (*nsd_flow_sink_ts)(const nsd_flowt *rows, uint32_t n, void *user);
+long nsd_pcap_flows_expire_ts(const char *path, int mode, const struct nsd_bpf_prog *filter,
+			      nsd_flow_table *t, uint32_t every, uint64_t idle_ns, uint32_t flags,
+			      nsd_flow_sink_ts sink, void *user);
+
 /* Pinned host memory for the pipe's buffers. */
 void *nsd_host_alloc(size_t len);
 void nsd_host_free(void *ptr);

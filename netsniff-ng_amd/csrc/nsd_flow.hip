@@ -11,7 +11,12 @@
 //                      packet p's, which any lane re-derives from the launch's
 //                      own inputs (nobody writes those);
 //   key[slots]  40 B : five u64 words (nsd_flow.h Key);
-//   cnt[slots]  40 B : pkts, bytes, first, last (u64), flags (u32).
+//   cnt[slots]  40 B : pkts, bytes, first, last (u64), flags (u32);
+//   tm[slots]   16 B : t_first, t_last (u64), the smallest / largest capture
+//                      timestamp of the flow's packets: a timed table only
+//                      (nsd_flow_create_timed, the header's "flow times"); a
+//                      plain table has no such array and its kernels are the
+//                      instantiations that never look for one.
 //
 // No lane ever waits on another lane's store: a slot is claimed with one
 // 32-bit CAS EMPTY -> packet index, and what a lane needs to compare against
@@ -36,6 +41,7 @@
 
 #include <algorithm>
 #include <new>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 
@@ -54,6 +60,9 @@ struct Cnt {
 };
 static_assert(sizeof(Cnt) == 40, "cnt row");
 static_assert(sizeof(nsd_flow) == 72, "nsd_flow");
+static_assert(sizeof(nsd_flowt) == 88 && offsetof(nsd_flowt, t_first) == 72, "nsd_flowt");
+static_assert(offsetof(nsd_flowt, pkts) == offsetof(nsd_flow, pkts) && offsetof(nsd_flowt, last) == offsetof(nsd_flow, last),
+	      "nsd_flowt begins as nsd_flow");
 
 // what the kernels need of a table
 struct Tab {
@@ -62,6 +71,7 @@ struct Tab {
 	Cnt *cnt;
 	uint64_t *stats;
 	uint32_t slots;
+	uint64_t *tm;   // two words per slot, or nullptr: a plain table
 };
 
 // one update's inputs
@@ -73,6 +83,7 @@ struct In {
 	uint32_t ext_words;
 	uint32_t n;
 	uint64_t base;
+	const uint64_t *ts;   // packet i's timestamp (the timed update), else nullptr
 };
 
 __device__ __forceinline__ int packet_key(const In &in, uint32_t i, Key &k, uint32_t &tflags, uint32_t &caplen)
@@ -102,17 +113,33 @@ __device__ __forceinline__ void accumulate(Cnt *c, uint64_t pkts, uint64_t bytes
 		(void)__hip_atomic_fetch_or(&c->flags, flags, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// the times of a slot of a timed table: min / max, whatever the order of the packets
+__device__ __forceinline__ void accumulate_times(uint64_t *tm, uint64_t t_first, uint64_t t_last)
+{
+	(void)__hip_atomic_fetch_min(&tm[0], t_first, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+	(void)__hip_atomic_fetch_max(&tm[1], t_last, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// a slot without a flow: what the sums, minima and maxima start from
+__device__ __forceinline__ void clear_slot(const Tab &t, uint64_t s)
+{
+	t.state[s] = EMPTY;
+	Cnt c;
+	c.pkts = c.bytes = c.last = 0;
+	c.first = UINT64_MAX;
+	c.flags = c.pad = 0;
+	t.cnt[s] = c;
+	if (t.tm) {
+		t.tm[2 * s] = UINT64_MAX;
+		t.tm[2 * s + 1] = 0;
+	}
+}
+
 __global__ __launch_bounds__(BLOCK) void flow_reset(Tab t)
 {
 	const uint64_t stride = (uint64_t)gridDim.x * BLOCK;
-	for (uint64_t s = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; s < t.slots; s += stride) {
-		t.state[s] = EMPTY;
-		Cnt c;
-		c.pkts = c.bytes = c.last = 0;
-		c.first = UINT64_MAX;
-		c.flags = c.pad = 0;
-		t.cnt[s] = c;
-	}
+	for (uint64_t s = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; s < t.slots; s += stride)
+		clear_slot(t, s);
 	if (blockIdx.x == 0 && threadIdx.x < NSD_FLOW_NSTATS)
 		t.stats[threadIdx.x] = 0;
 }
@@ -128,10 +155,28 @@ struct Agg {
 	uint32_t tag[AGG_N], pkts[AGG_N], first[AGG_N], last[AGG_N], flags[AGG_N];
 	unsigned long long bytes[AGG_N];
 };
+// The timed update's entries carry the flow's two times as well.  They are
+// whole 64-bit values of any epoch (0 and UINT64_MAX included, and a file's
+// need not ascend), so there is no 32-bit form of them as there is of first /
+// last: 64-bit LDS min / max, 8 KB more per block.
+struct AggTimes {
+	unsigned long long tmin[AGG_N], tmax[AGG_N];
+};
+template <bool TIMED>
+struct AggMem {
+	Agg a;
+};
+template <>
+struct AggMem<true> {
+	Agg a;
+	AggTimes tt;
+};
 
-__device__ __forceinline__ void add_flow(const Tab &t, const In &in, Agg *agg, uint32_t slot, uint32_t pkts,
-					 uint32_t bytes, uint32_t first, uint32_t last, uint32_t flags)
+template <bool TIMED>
+__device__ __forceinline__ void add_flow(const Tab &t, const In &in, AggMem<TIMED> *mem, uint32_t slot, uint32_t pkts,
+					 uint32_t bytes, uint32_t first, uint32_t last, uint32_t flags, uint64_t ts)
 {
+	Agg *agg = &mem->a;
 	const uint32_t e = slot & (AGG_N - 1);
 	const uint32_t old = atomicCAS(&agg->tag[e], NOSLOT, slot);
 	if (old == NOSLOT || old == slot) {
@@ -141,23 +186,36 @@ __device__ __forceinline__ void add_flow(const Tab &t, const In &in, Agg *agg, u
 		atomicMax(&agg->last[e], last);
 		if (flags)
 			atomicOr(&agg->flags[e], flags);
+		if constexpr (TIMED) {
+			atomicMin(&mem->tt.tmin[e], (unsigned long long)ts);
+			atomicMax(&mem->tt.tmax[e], (unsigned long long)ts);
+		}
 		return;
 	}
 	accumulate(&t.cnt[slot], pkts, bytes, in.base + first, in.base + last, flags);
+	if constexpr (TIMED)
+		accumulate_times(t.tm + 2ull * slot, ts, ts);
 }
 
 // One packet per lane, grid-stride; the rounds are wave-uniform, so the
 // stats are ballots over whole waves.  The block sums in LDS (above) and
-// adds its entries to the table after its last packet.
+// adds its entries to the table after its last packet.  TIMED: a timed table
+// and in.ts; a packet that is counted (it found its flow's slot) gives its
+// timestamp to the flow's minimum and maximum, the others' are not read.
+template <bool TIMED>
 __global__ __launch_bounds__(BLOCK) void flow_update(Tab t, In in)
 {
-	__shared__ Agg agg_mem;
-	Agg *agg = &agg_mem;
+	__shared__ AggMem<TIMED> agg_mem;
+	Agg *agg = &agg_mem.a;
 	for (uint32_t e = threadIdx.x; e < AGG_N; e += BLOCK) {
 		agg->tag[e] = NOSLOT;
 		agg->pkts[e] = agg->last[e] = agg->flags[e] = 0;
 		agg->first[e] = 0xFFFFFFFFu;
 		agg->bytes[e] = 0;
+		if constexpr (TIMED) {
+			agg_mem.tt.tmin[e] = ~0ull;
+			agg_mem.tt.tmax[e] = 0;
+		}
 	}
 	__syncthreads();
 	const uint32_t lane = threadIdx.x & 63;
@@ -218,8 +276,12 @@ __global__ __launch_bounds__(BLOCK) void flow_update(Tab t, In in)
 		w_skip += (uint32_t)__popcll(__ballot(st == K_SKIPPED));
 		w_full += (uint32_t)__popcll(__ballot(keyed && !found));
 		w_new += (uint32_t)__popcll(__ballot(fresh));
-		if (found)
-			add_flow(t, in, agg, slot, 1, caplen, (uint32_t)i, (uint32_t)i, tflags);
+		if (found) {
+			uint64_t ts = 0;
+			if constexpr (TIMED)
+				ts = in.ts[i];
+			add_flow<TIMED>(t, in, &agg_mem, slot, 1, caplen, (uint32_t)i, (uint32_t)i, tflags, ts);
+		}
 	}
 	if (lane == 0) {
 		if (w_pkts)
@@ -238,9 +300,12 @@ __global__ __launch_bounds__(BLOCK) void flow_update(Tab t, In in)
 	__syncthreads();
 	for (uint32_t e = threadIdx.x; e < AGG_N; e += BLOCK) {
 		const uint32_t slot = agg->tag[e];
-		if (slot < t.slots)
+		if (slot < t.slots) {
 			accumulate(&t.cnt[slot], agg->pkts[e], agg->bytes[e], in.base + agg->first[e], in.base + agg->last[e],
 				   agg->flags[e]);
+			if constexpr (TIMED)
+				accumulate_times(t.tm + 2ull * slot, agg_mem.tt.tmin[e], agg_mem.tt.tmax[e]);
+		}
 	}
 }
 
@@ -270,10 +335,13 @@ __global__ __launch_bounds__(BLOCK) void flow_commit(Tab t, In in)
 }
 
 // Occupied slots packed into `out` through a wave-aggregated cursor (*count,
-// zeroed before the launch); rows past `max` are counted, not written.
+// zeroed before the launch); rows past `max` are counted, not written.  TS:
+// nsd_flowt rows, the slot's two times after the nine words of nsd_flow.
+template <bool TS>
 __global__ __launch_bounds__(BLOCK) void flow_export(Tab t, uint64_t *out, uint32_t max, uint32_t *count,
 						     uint64_t *stats_out)
 {
+	constexpr uint64_t ROW = TS ? 11 : 9;
 	const uint32_t lane = threadIdx.x & 63;
 	const uint64_t stride = (uint64_t)gridDim.x * BLOCK;
 #pragma unroll 1
@@ -291,7 +359,7 @@ __global__ __launch_bounds__(BLOCK) void flow_export(Tab t, uint64_t *out, uint3
 		if (occ && pos < max) {
 			const uint64_t *kp = t.key + 5ull * s;
 			const Cnt c = t.cnt[s];
-			uint64_t *o = out + 9ull * pos;
+			uint64_t *o = out + ROW * pos;
 			o[0] = kp[0];
 			o[1] = kp[1];
 			o[2] = kp[2];
@@ -301,6 +369,10 @@ __global__ __launch_bounds__(BLOCK) void flow_export(Tab t, uint64_t *out, uint3
 			o[6] = c.bytes;
 			o[7] = c.first;
 			o[8] = c.last;
+			if constexpr (TS) {
+				o[9] = t.tm[2 * s];
+				o[10] = t.tm[2 * s + 1];
+			}
 		}
 	}
 	if (blockIdx.x == 0 && threadIdx.x < NSD_FLOW_NSTATS)
@@ -582,9 +654,12 @@ __global__ __launch_bounds__(64) void conv_scan(ConvWs w, uint32_t k, int d)
 
 // Candidates above the threshold, and `rem` of those equal to it (more can tie
 // only when bases were reused), write their row: positions 0 .. k - rem - 1
-// and k - rem .. k - 1, each through a wave-aggregated cursor.
+// and k - rem .. k - 1, each through a wave-aggregated cursor.  TS: nsd_convt
+// rows, the smaller t_first and the larger t_last of the row's slot and `rev`.
+template <bool TS>
 __global__ __launch_bounds__(BLOCK) void conv_gather(Tab t, ConvWs w, uint32_t k, uint64_t *out, uint32_t *count)
 {
+	constexpr uint64_t ROW = TS ? 13 : 11;
 	ConvHdr *h = w.h;
 	const uint32_t n = conv_ncand(w);
 	if (blockIdx.x == 0 && threadIdx.x == 0) {
@@ -640,7 +715,7 @@ __global__ __launch_bounds__(BLOCK) void conv_gather(Tab t, ConvWs w, uint32_t k
 		e.flags = 0;
 		if (r != NOSLOT)
 			e = t.cnt[r];
-		uint64_t *o = out + 11ull * pos;
+		uint64_t *o = out + ROW * pos;
 		o[0] = kp[0];
 		o[1] = kp[1];
 		o[2] = kp[2];
@@ -652,6 +727,16 @@ __global__ __launch_bounds__(BLOCK) void conv_gather(Tab t, ConvWs w, uint32_t k
 		o[8] = e.bytes;
 		o[9] = c.first < e.first ? c.first : e.first;
 		o[10] = c.last > e.last ? c.last : e.last;
+		if constexpr (TS) {
+			uint64_t tf = t.tm[2ull * s], tl = t.tm[2ull * s + 1];
+			if (r != NOSLOT) {
+				const uint64_t rf = t.tm[2ull * r], rl = t.tm[2ull * r + 1];
+				tf = rf < tf ? rf : tf;
+				tl = rl > tl ? rl : tl;
+			}
+			o[11] = tf;
+			o[12] = tl;
+		}
 	}
 }
 
@@ -674,9 +759,13 @@ __global__ __launch_bounds__(BLOCK) void conv_gather(Tab t, ConvWs w, uint32_t k
 // The flows removed are min(qualified, max): the positions below `max`.
 //
 // Workspace: an EXP_HDR-byte header, then the survivors' rows, 80 bytes each:
-// the five key words, then the Cnt.  The kernels bound the counts they read
-// from the header by `slots`.
+// the five key words, then the Cnt; on a timed table (TT) 96 bytes, the two
+// times after them, whichever criterion the call uses.  The kernels bound the
+// counts they read from the header by `slots`.
+// BY_TIME (a timed table's nsd_flow_expire_device_ts): the criterion is t_last
+// where it is `last` otherwise, and the rows that leave are nsd_flowt.
 constexpr size_t EXP_HDR = 2048;
+constexpr uint64_t exp_row_words(bool tt) { return tt ? 12 : 10; }
 
 struct ExpHdr {
 	uint32_t qualified;   // expire_split's cursor of qualifying flows
@@ -688,7 +777,7 @@ static_assert(sizeof(ExpHdr) <= EXP_HDR, "expire header");
 
 struct ExpWs {
 	ExpHdr *h;
-	uint64_t *rows;   // 10 words per survivor
+	uint64_t *rows;   // exp_row_words() per survivor
 	uint32_t slots;
 };
 
@@ -721,9 +810,12 @@ __device__ __forceinline__ uint64_t wave_cursor(uint32_t *cursor, uint64_t m, ui
 }
 
 // One slot per lane, grid-stride; only reads the table.
+template <bool TT, bool BY_TIME>
 __global__ __launch_bounds__(BLOCK) void expire_split(Tab t, ExpWs w, uint64_t before, uint32_t flags, uint64_t *out,
 						      uint32_t max)
 {
+	static_assert(TT || !BY_TIME, "times only on a timed table");
+	constexpr uint64_t ROW = BY_TIME ? 11 : 9, KEEP = exp_row_words(TT);
 	const uint32_t lane = threadIdx.x & 63;
 	const uint64_t stride = (uint64_t)gridDim.x * BLOCK;
 #pragma unroll 1
@@ -735,17 +827,22 @@ __global__ __launch_bounds__(BLOCK) void expire_split(Tab t, ExpWs w, uint64_t b
 		Key k;
 		Cnt c;
 		bool idle = false;
+		uint64_t tf = 0, tl = 0;
 		if (occ) {
 			load_key(t, (uint32_t)s, k);
 			c = t.cnt[s];
-			idle = c.last < before;
+			if constexpr (TT) {
+				tf = t.tm[2 * s];
+				tl = t.tm[2 * s + 1];
+			}
+			idle = (BY_TIME ? tl : c.last) < before;
 			if (idle && (flags & NSD_FLOW_EXPIRE_PAIRED)) {
 				Key r;
 				reverse_key(k, r);
 				if (!key_eq(k, r)) {
 					const uint32_t rev = find_key(t, r);
 					if (rev != NOSLOT)
-						idle = t.cnt[rev].last < before;
+						idle = (BY_TIME ? t.tm[2ull * rev + 1] : t.cnt[rev].last) < before;
 				}
 			}
 		}
@@ -755,7 +852,7 @@ __global__ __launch_bounds__(BLOCK) void expire_split(Tab t, ExpWs w, uint64_t b
 			const uint64_t pos = wave_cursor(&w.h->qualified, mq, lane);
 			if (idle) {
 				if (pos < max) {
-					uint64_t *o = out + 9ull * pos;
+					uint64_t *o = out + ROW * pos;
 					o[0] = k.w[0];
 					o[1] = k.w[1];
 					o[2] = k.w[2];
@@ -765,6 +862,10 @@ __global__ __launch_bounds__(BLOCK) void expire_split(Tab t, ExpWs w, uint64_t b
 					o[6] = c.bytes;
 					o[7] = c.first;
 					o[8] = c.last;
+					if constexpr (BY_TIME) {
+						o[9] = tf;
+						o[10] = tl;
+					}
 				} else {
 					stay = true;   // no room for its row: it stays as it is
 				}
@@ -776,7 +877,7 @@ __global__ __launch_bounds__(BLOCK) void expire_split(Tab t, ExpWs w, uint64_t b
 		const uint64_t pos = wave_cursor(&w.h->survivors, ms, lane);
 		// (max = 0 removes nothing: the rows would not be read)
 		if (stay && max && pos < t.slots) {
-			uint64_t *o = w.rows + 10ull * pos;
+			uint64_t *o = w.rows + KEEP * pos;
 			o[0] = k.w[0];
 			o[1] = k.w[1];
 			o[2] = k.w[2];
@@ -787,6 +888,10 @@ __global__ __launch_bounds__(BLOCK) void expire_split(Tab t, ExpWs w, uint64_t b
 			o[7] = c.first;
 			o[8] = c.last;
 			o[9] = c.flags;
+			if constexpr (TT) {
+				o[10] = tf;
+				o[11] = tl;
+			}
 		}
 	}
 }
@@ -808,22 +913,18 @@ __global__ __launch_bounds__(BLOCK) void expire_clear(Tab t, ExpWs w, uint32_t m
 	if (!removed)
 		return;
 	const uint64_t stride = (uint64_t)gridDim.x * BLOCK;
-	for (uint64_t s = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; s < t.slots; s += stride) {
-		t.state[s] = EMPTY;
-		Cnt c;
-		c.pkts = c.bytes = c.last = 0;
-		c.first = UINT64_MAX;
-		c.flags = c.pad = 0;
-		t.cnt[s] = c;
-	}
+	for (uint64_t s = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; s < t.slots; s += stride)
+		clear_slot(t, s);
 }
 
 // One survivor per lane, grid-stride.  Keys are unique, so a lane never
 // compares against a slot: it takes the first EMPTY one of its probe (one
 // relaxed CAS; a slot another lane took is passed by) and stores its own rows
 // there with plain stores, which nobody reads before the next kernel.
+template <bool TT>
 __global__ __launch_bounds__(BLOCK) void expire_reinsert(Tab t, ExpWs w, uint32_t max)
 {
+	constexpr uint64_t KEEP = exp_row_words(TT);
 	if (!expire_removed(w, max))
 		return;
 	const uint32_t n = expire_survivors(w);
@@ -831,7 +932,7 @@ __global__ __launch_bounds__(BLOCK) void expire_reinsert(Tab t, ExpWs w, uint32_
 	const uint64_t stride = (uint64_t)gridDim.x * BLOCK;
 #pragma unroll 1
 	for (uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; i < n; i += stride) {
-		const uint64_t *r = w.rows + 10ull * i;
+		const uint64_t *r = w.rows + KEEP * i;
 		Key k;
 		for (int j = 0; j < 5; j++)
 			k.w[j] = r[j];
@@ -862,6 +963,10 @@ __global__ __launch_bounds__(BLOCK) void expire_reinsert(Tab t, ExpWs w, uint32_
 		c.flags = (uint32_t)r[9];
 		c.pad = 0;
 		t.cnt[slot] = c;
+		if constexpr (TT) {
+			t.tm[2ull * slot] = r[10];
+			t.tm[2ull * slot + 1] = r[11];
+		}
 	}
 }
 
@@ -878,12 +983,13 @@ struct Stage {
 	uint8_t *bpf_ws = nullptr; size_t bpf_ws_cap = 0;
 	nsd_sll_t *sll = nullptr; size_t sll_cap = 0;
 	uint8_t *misc = nullptr; size_t misc_cap = 0;   // ext_used | count | counters
+	uint64_t *ts = nullptr; size_t ts_cap = 0;      // (a timed table's feeds)
 
 	void release()
 	{
 		(void)hipFree(frames); (void)hipFree(desc); (void)hipFree(desc_out); (void)hipFree(verdict);
 		(void)hipFree(rec); (void)hipFree(ext); (void)hipFree(ws); (void)hipFree(bpf_ws); (void)hipFree(sll);
-		(void)hipFree(misc);
+		(void)hipFree(misc); (void)hipFree(ts);
 		*this = Stage();
 	}
 };
@@ -895,6 +1001,7 @@ using namespace nsdflow;
 struct nsd_flow_table {
 	Tab tab{};
 	void *mem = nullptr;
+	bool timed = false;   // tab.tm is there: the _ts entries, and no plain update
 	int cus = 0;
 	hipStream_t last = nullptr;   // the stream of the last enqueued call
 	Stage stage;
@@ -919,7 +1026,9 @@ extern "C" int nsd_flow_reset(nsd_flow_table *t, void *stream)
 	return hip_ok(hipGetLastError(), "launch") ? NSD_OK : NSD_ERR_HIP;
 }
 
-extern "C" nsd_flow_table *nsd_flow_create(uint32_t max_flows)
+extern "C" int nsd_flow_is_timed(const nsd_flow_table *t) { return t && t->timed; }
+
+static nsd_flow_table *create_table(uint32_t max_flows, bool timed)
 {
 	if (max_flows == 0 || max_flows > (1u << 30))
 		return nullptr;
@@ -937,11 +1046,11 @@ extern "C" nsd_flow_table *nsd_flow_create(uint32_t max_flows)
 	hipDeviceProp_t prop;
 	if (hip_ok(hipGetDevice(&dev), "hipGetDevice") && hip_ok(hipGetDeviceProperties(&prop, dev), "props"))
 		t->cus = prop.multiProcessorCount;
-	// one allocation: state | stats | key | cnt
+	// one allocation: state | stats | key | cnt, and behind them a timed table's tm
 	const size_t a = 256;
 	auto up = [&](size_t v) { return (v + a - 1) & ~(a - 1); };
 	const size_t o_state = 0, o_misc = up((size_t)slots * 4), o_key = o_misc + a, o_cnt = o_key + up((size_t)slots * 40), total = o_cnt + up((size_t)slots * 40);
-	if (!hip_ok(hipMalloc(&t->mem, total), "hipMalloc")) {
+	if (!hip_ok(hipMalloc(&t->mem, total + (timed ? (size_t)slots * 16 : 0)), "hipMalloc")) {
 		delete t;
 		return nullptr;
 	}
@@ -951,6 +1060,8 @@ extern "C" nsd_flow_table *nsd_flow_create(uint32_t max_flows)
 	t->tab.key = (uint64_t *)(m + o_key);
 	t->tab.cnt = (Cnt *)(m + o_cnt);
 	t->tab.slots = slots;
+	t->tab.tm = timed ? (uint64_t *)(m + total) : nullptr;
+	t->timed = timed;
 	if (nsd_flow_reset(t, nullptr) != NSD_OK || !hip_ok(hipStreamSynchronize(nullptr), "sync")) {
 		(void)hipFree(t->mem);
 		delete t;
@@ -958,6 +1069,9 @@ extern "C" nsd_flow_table *nsd_flow_create(uint32_t max_flows)
 	}
 	return t;
 }
+
+extern "C" nsd_flow_table *nsd_flow_create(uint32_t max_flows) { return create_table(max_flows, false); }
+extern "C" nsd_flow_table *nsd_flow_create_timed(uint32_t max_flows) { return create_table(max_flows, true); }
 
 extern "C" void nsd_flow_destroy(nsd_flow_table *t)
 {
@@ -969,23 +1083,68 @@ extern "C" void nsd_flow_destroy(nsd_flow_table *t)
 	delete t;
 }
 
+// The entries come in two forms, the plain one and the _ts one with the times
+// (the header's "flow times"); each pair shares its body.  `ts` = the _ts form
+// was called: on a plain table that is NSD_ERR_ARG, and so is the plain update
+// on a timed table (its flows would be left without times).
+template <class Row>
+constexpr bool with_times()
+{
+	return std::is_same<Row, nsd_flowt>::value || std::is_same<Row, nsd_convt>::value;
+}
+
+static int update_device(nsd_flow_table *t, const uint8_t *d_frames, const nsd_desc_t *d_desc, uint32_t n,
+			 const nsd_rec *d_rec, const uint32_t *d_ext, uint32_t ext_words, const uint64_t *d_ts, bool ts,
+			 uint64_t base, void *stream)
+{
+	if (!t || n > MAX_N || ts != t->timed)
+		return NSD_ERR_ARG;
+	if (n == 0)
+		return NSD_OK;
+	if (!d_frames || !d_desc || !d_rec || (ext_words && !d_ext) || (ts && !d_ts))
+		return NSD_ERR_ARG;
+	if (((uintptr_t)d_rec & 15) || ((uintptr_t)d_desc & 7) || ((uintptr_t)d_ext & 3) || ((uintptr_t)d_ts & 7))
+		return NSD_ERR_ARG;
+	hipStream_t s = (hipStream_t)stream;
+	const In in{ d_frames, (const uint64_t *)d_desc, d_rec, ext_words ? d_ext : nullptr, ext_words, n, base,
+		     ts ? d_ts : nullptr };
+	const dim3 grid(grid_for(t, n)), block(BLOCK);
+	if (ts)
+		hipLaunchKernelGGL(flow_update<true>, grid, block, 0, s, t->tab, in);
+	else
+		hipLaunchKernelGGL(flow_update<false>, grid, block, 0, s, t->tab, in);
+	hipLaunchKernelGGL(flow_commit, dim3(grid_for(t, t->tab.slots)), block, 0, s, t->tab, in);
+	t->last = s;
+	return hip_ok(hipGetLastError(), "launch") ? NSD_OK : NSD_ERR_HIP;
+}
+
 extern "C" int nsd_flow_update_device(nsd_flow_table *t, const uint8_t *d_frames, const nsd_desc_t *d_desc,
 				      uint32_t n, const nsd_rec *d_rec, const uint32_t *d_ext, uint32_t ext_words,
 				      uint64_t base, void *stream)
 {
-	if (!t || n > MAX_N)
-		return NSD_ERR_ARG;
-	if (n == 0)
-		return NSD_OK;
-	if (!d_frames || !d_desc || !d_rec || (ext_words && !d_ext))
-		return NSD_ERR_ARG;
-	if (((uintptr_t)d_rec & 15) || ((uintptr_t)d_desc & 7) || ((uintptr_t)d_ext & 3))
+	return update_device(t, d_frames, d_desc, n, d_rec, d_ext, ext_words, nullptr, false, base, stream);
+}
+
+extern "C" int nsd_flow_update_device_ts(nsd_flow_table *t, const uint8_t *d_frames, const nsd_desc_t *d_desc,
+					 uint32_t n, const nsd_rec *d_rec, const uint32_t *d_ext, uint32_t ext_words,
+					 const uint64_t *d_ts, uint64_t base, void *stream)
+{
+	return update_device(t, d_frames, d_desc, n, d_rec, d_ext, ext_words, d_ts, true, base, stream);
+}
+
+static int export_device(nsd_flow_table *t, void *d_flows, uint32_t max, uint32_t *d_count, uint64_t *d_stats,
+			 void *stream, bool ts)
+{
+	if (!t || (ts && !t->timed) || !d_count || !d_stats || (max && !d_flows) || ((uintptr_t)d_flows & 7))
 		return NSD_ERR_ARG;
 	hipStream_t s = (hipStream_t)stream;
-	const In in{ d_frames, (const uint64_t *)d_desc, d_rec, ext_words ? d_ext : nullptr, ext_words, n, base };
-	const dim3 grid(grid_for(t, n)), block(BLOCK);
-	hipLaunchKernelGGL(flow_update, grid, block, 0, s, t->tab, in);
-	hipLaunchKernelGGL(flow_commit, dim3(grid_for(t, t->tab.slots)), block, 0, s, t->tab, in);
+	if (!hip_ok(hipMemsetAsync(d_count, 0, 4, s), "memset"))
+		return NSD_ERR_HIP;
+	const dim3 grid(grid_for(t, t->tab.slots)), block(BLOCK);
+	if (ts)
+		hipLaunchKernelGGL(flow_export<true>, grid, block, 0, s, t->tab, (uint64_t *)d_flows, max, d_count, d_stats);
+	else
+		hipLaunchKernelGGL(flow_export<false>, grid, block, 0, s, t->tab, (uint64_t *)d_flows, max, d_count, d_stats);
 	t->last = s;
 	return hip_ok(hipGetLastError(), "launch") ? NSD_OK : NSD_ERR_HIP;
 }
@@ -993,25 +1152,25 @@ extern "C" int nsd_flow_update_device(nsd_flow_table *t, const uint8_t *d_frames
 extern "C" int nsd_flow_export_device(nsd_flow_table *t, nsd_flow *d_flows, uint32_t max, uint32_t *d_count,
 				      uint64_t *d_stats, void *stream)
 {
-	if (!t || !d_count || !d_stats || (max && !d_flows) || ((uintptr_t)d_flows & 7))
-		return NSD_ERR_ARG;
-	hipStream_t s = (hipStream_t)stream;
-	if (!hip_ok(hipMemsetAsync(d_count, 0, 4, s), "memset"))
-		return NSD_ERR_HIP;
-	hipLaunchKernelGGL(flow_export, dim3(grid_for(t, t->tab.slots)), dim3(BLOCK), 0, s, t->tab, (uint64_t *)d_flows,
-			   max, d_count, d_stats);
-	t->last = s;
-	return hip_ok(hipGetLastError(), "launch") ? NSD_OK : NSD_ERR_HIP;
+	return export_device(t, d_flows, max, d_count, d_stats, stream, false);
 }
 
-static void sort_by_first(std::vector<nsd_flow> &v)
+extern "C" int nsd_flow_export_device_ts(nsd_flow_table *t, nsd_flowt *d_flows, uint32_t max, uint32_t *d_count,
+					 uint64_t *d_stats, void *stream)
 {
-	std::sort(v.begin(), v.end(), [](const nsd_flow &a, const nsd_flow &b) { return a.first < b.first; });
+	return export_device(t, d_flows, max, d_count, d_stats, stream, true);
 }
 
-extern "C" long nsd_flow_export(nsd_flow_table *t, nsd_flow *flows, uint32_t max, uint64_t *stats)
+template <class Row>
+static void sort_by_first(std::vector<Row> &v)
 {
-	if (!t || (max && !flows))
+	std::sort(v.begin(), v.end(), [](const Row &a, const Row &b) { return a.first < b.first; });
+}
+
+template <class Row>
+static long export_host(nsd_flow_table *t, Row *flows, uint32_t max, uint64_t *stats)
+{
+	if (!t || (with_times<Row>() && !t->timed) || (max && !flows))
 		return NSD_ERR_ARG;
 	hipStream_t s = t->last;
 	uint64_t st[NSD_FLOW_NSTATS];
@@ -1020,17 +1179,17 @@ extern "C" long nsd_flow_export(nsd_flow_table *t, nsd_flow *flows, uint32_t max
 		return NSD_ERR_HIP;
 	const uint32_t have = (uint32_t)st[NSD_FLOW_ST_FLOWS];
 	uint8_t *d = nullptr;
-	if (!hip_ok(hipMalloc(&d, 256 + (size_t)have * sizeof(nsd_flow)), "hipMalloc"))
+	if (!hip_ok(hipMalloc(&d, 256 + (size_t)have * sizeof(Row)), "hipMalloc"))
 		return NSD_ERR_NOMEM;
 	uint32_t *d_count = (uint32_t *)d;
 	uint64_t *d_stats = (uint64_t *)(d + 64);
-	nsd_flow *d_flows = (nsd_flow *)(d + 256);
-	std::vector<nsd_flow> rows(have);
+	Row *d_flows = (Row *)(d + 256);
+	std::vector<Row> rows(have);
 	uint32_t count = 0;
-	bool ok = nsd_flow_export_device(t, d_flows, have, d_count, d_stats, s) == NSD_OK &&
+	bool ok = export_device(t, d_flows, have, d_count, d_stats, s, with_times<Row>()) == NSD_OK &&
 		  hip_ok(hipMemcpyAsync(&count, d_count, 4, hipMemcpyDeviceToHost, s), "D2H") &&
 		  hip_ok(hipMemcpyAsync(st, d_stats, sizeof(st), hipMemcpyDeviceToHost, s), "D2H") &&
-		  (!have || hip_ok(hipMemcpyAsync(rows.data(), d_flows, (size_t)have * sizeof(nsd_flow),
+		  (!have || hip_ok(hipMemcpyAsync(rows.data(), d_flows, (size_t)have * sizeof(Row),
 						  hipMemcpyDeviceToHost, s), "D2H")) &&
 		  hip_ok(hipStreamSynchronize(s), "sync");
 	(void)hipFree(d);
@@ -1039,10 +1198,20 @@ extern "C" long nsd_flow_export(nsd_flow_table *t, nsd_flow *flows, uint32_t max
 	sort_by_first(rows);
 	const uint32_t k = have < max ? have : max;
 	if (k)
-		memcpy(flows, rows.data(), (size_t)k * sizeof(nsd_flow));
+		memcpy(flows, rows.data(), (size_t)k * sizeof(Row));
 	if (stats)
 		memcpy(stats, st, sizeof(st));
 	return (long)have;
+}
+
+extern "C" long nsd_flow_export(nsd_flow_table *t, nsd_flow *flows, uint32_t max, uint64_t *stats)
+{
+	return export_host(t, flows, max, stats);
+}
+
+extern "C" long nsd_flow_export_ts(nsd_flow_table *t, nsd_flowt *flows, uint32_t max, uint64_t *stats)
+{
+	return export_host(t, flows, max, stats);
 }
 
 // ---- conversations: the entries ---------------------------------------------
@@ -1054,10 +1223,10 @@ extern "C" size_t nsd_flow_conv_workspace_bytes(const nsd_flow_table *t)
 }
 
 // init | pair | per digit: hist, scan | gather: a linear chain of kernels on `stream`
-extern "C" int nsd_flow_conv_device(nsd_flow_table *t, int by, uint32_t k, nsd_conv *d_conv, uint32_t *d_count,
-				    void *d_workspace, void *stream)
+static int conv_device(nsd_flow_table *t, int by, uint32_t k, void *d_conv, uint32_t *d_count, void *d_workspace,
+		       void *stream, bool ts)
 {
-	if (!t || by < NSD_CONV_BY_FIRST || by > NSD_CONV_BY_PKTS || !d_count || !d_workspace ||
+	if (!t || (ts && !t->timed) || by < NSD_CONV_BY_FIRST || by > NSD_CONV_BY_PKTS || !d_count || !d_workspace ||
 	    (k && !d_conv) || ((uintptr_t)d_conv & 7) || ((uintptr_t)d_workspace & 15) || ((uintptr_t)d_count & 3))
 		return NSD_ERR_ARG;
 	hipStream_t s = (hipStream_t)stream;
@@ -1080,15 +1249,31 @@ extern "C" int nsd_flow_conv_device(nsd_flow_table *t, int by, uint32_t k, nsd_c
 			hipLaunchKernelGGL(conv_scan, dim3(1), dim3(64), 0, s, w, k, d);
 		}
 	}
-	hipLaunchKernelGGL(conv_gather, grid, block, 0, s, t->tab, w, k, (uint64_t *)d_conv, d_count);
+	if (ts)
+		hipLaunchKernelGGL(conv_gather<true>, grid, block, 0, s, t->tab, w, k, (uint64_t *)d_conv, d_count);
+	else
+		hipLaunchKernelGGL(conv_gather<false>, grid, block, 0, s, t->tab, w, k, (uint64_t *)d_conv, d_count);
 	t->last = s;
 	return hip_ok(hipGetLastError(), "launch") ? NSD_OK : NSD_ERR_HIP;
 }
 
-// the total order of the header: `by`'s metric descending, then first ascending
-static void sort_conv(std::vector<nsd_conv> &v, int by)
+extern "C" int nsd_flow_conv_device(nsd_flow_table *t, int by, uint32_t k, nsd_conv *d_conv, uint32_t *d_count,
+				    void *d_workspace, void *stream)
 {
-	std::sort(v.begin(), v.end(), [by](const nsd_conv &a, const nsd_conv &b) {
+	return conv_device(t, by, k, d_conv, d_count, d_workspace, stream, false);
+}
+
+extern "C" int nsd_flow_conv_device_ts(nsd_flow_table *t, int by, uint32_t k, nsd_convt *d_conv, uint32_t *d_count,
+				       void *d_workspace, void *stream)
+{
+	return conv_device(t, by, k, d_conv, d_count, d_workspace, stream, true);
+}
+
+// the total order of the header: `by`'s metric descending, then first ascending
+template <class Conv>
+static void sort_conv(std::vector<Conv> &v, int by)
+{
+	std::sort(v.begin(), v.end(), [by](const Conv &a, const Conv &b) {
 		if (by != NSD_CONV_BY_FIRST) {
 			const uint64_t ma = by == NSD_CONV_BY_BYTES ? a.bytes_src + a.bytes_dst : a.pkts_src + a.pkts_dst;
 			const uint64_t mb = by == NSD_CONV_BY_BYTES ? b.bytes_src + b.bytes_dst : b.pkts_src + b.pkts_dst;
@@ -1099,9 +1284,10 @@ static void sort_conv(std::vector<nsd_conv> &v, int by)
 	});
 }
 
-extern "C" long nsd_flow_conversations(nsd_flow_table *t, int by, uint32_t k, nsd_conv *conv, uint64_t *stats)
+template <class Conv>
+static long conversations_host(nsd_flow_table *t, int by, uint32_t k, Conv *conv, uint64_t *stats)
 {
-	if (!t || by < NSD_CONV_BY_FIRST || by > NSD_CONV_BY_PKTS || (k && !conv))
+	if (!t || (with_times<Conv>() && !t->timed) || by < NSD_CONV_BY_FIRST || by > NSD_CONV_BY_PKTS || (k && !conv))
 		return NSD_ERR_ARG;
 	hipStream_t s = t->last;
 	uint64_t st[NSD_FLOW_NSTATS];
@@ -1110,62 +1296,99 @@ extern "C" long nsd_flow_conversations(nsd_flow_table *t, int by, uint32_t k, ns
 		return NSD_ERR_HIP;
 	// (no more conversations than flows)
 	const uint32_t have = (uint32_t)st[NSD_FLOW_ST_FLOWS], want = k < have ? k : have;
-	const size_t o_rows = 256, o_ws = (o_rows + (size_t)want * sizeof(nsd_conv) + 255) & ~(size_t)255;
+	const size_t o_rows = 256, o_ws = (o_rows + (size_t)want * sizeof(Conv) + 255) & ~(size_t)255;
 	uint8_t *d = nullptr;
 	if (!hip_ok(hipMalloc(&d, o_ws + nsd_flow_conv_workspace_bytes(t)), "hipMalloc"))
 		return NSD_ERR_NOMEM;
 	uint32_t *d_count = (uint32_t *)d;
-	nsd_conv *d_rows = (nsd_conv *)(d + o_rows);
+	Conv *d_rows = (Conv *)(d + o_rows);
 	uint32_t count[2] = { 0, 0 };
-	std::vector<nsd_conv> rows;
-	bool ok = nsd_flow_conv_device(t, by, want, d_rows, d_count, d + o_ws, s) == NSD_OK &&
+	std::vector<Conv> rows;
+	bool ok = conv_device(t, by, want, d_rows, d_count, d + o_ws, s, with_times<Conv>()) == NSD_OK &&
 		  hip_ok(hipMemcpyAsync(count, d_count, 8, hipMemcpyDeviceToHost, s), "D2H") &&
 		  hip_ok(hipStreamSynchronize(s), "sync") && count[0] <= want;
 	if (ok && count[0]) {
 		rows.resize(count[0]);
-		ok = hip_ok(hipMemcpy(rows.data(), d_rows, (size_t)count[0] * sizeof(nsd_conv), hipMemcpyDeviceToHost), "D2H");
+		ok = hip_ok(hipMemcpy(rows.data(), d_rows, (size_t)count[0] * sizeof(Conv), hipMemcpyDeviceToHost), "D2H");
 	}
 	(void)hipFree(d);
 	if (!ok)
 		return NSD_ERR_HIP;
 	sort_conv(rows, by);
 	if (!rows.empty())
-		memcpy(conv, rows.data(), rows.size() * sizeof(nsd_conv));
+		memcpy(conv, rows.data(), rows.size() * sizeof(Conv));
 	if (stats)
 		memcpy(stats, st, sizeof(st));
 	return (long)count[1];
 }
 
+extern "C" long nsd_flow_conversations(nsd_flow_table *t, int by, uint32_t k, nsd_conv *conv, uint64_t *stats)
+{
+	return conversations_host(t, by, k, conv, stats);
+}
+
+extern "C" long nsd_flow_conversations_ts(nsd_flow_table *t, int by, uint32_t k, nsd_convt *conv, uint64_t *stats)
+{
+	return conversations_host(t, by, k, conv, stats);
+}
+
 // ---- expiry: the entries ------------------------------------------------------
 extern "C" size_t nsd_flow_expire_workspace_bytes(const nsd_flow_table *t)
 {
-	return t ? EXP_HDR + 80 * (size_t)t->tab.slots : 0;
+	return t ? EXP_HDR + 8 * exp_row_words(t->timed) * (size_t)t->tab.slots : 0;
 }
 
-// init | split | clear | reinsert: a linear chain of kernels on `stream`
-extern "C" int nsd_flow_expire_device(nsd_flow_table *t, uint64_t before, uint32_t flags, nsd_flow *d_expired,
-				      uint32_t max, uint32_t *d_count, void *d_workspace, void *stream)
+// init | split | clear | reinsert: a linear chain of kernels on `stream`.  A
+// timed table's survivors carry their times through the workspace under
+// either criterion.
+static int expire_device(nsd_flow_table *t, uint64_t before, uint32_t flags, void *d_expired, uint32_t max,
+			 uint32_t *d_count, void *d_workspace, void *stream, bool ts)
 {
-	if (!t || (flags & ~NSD_FLOW_EXPIRE_PAIRED) || !d_count || !d_workspace || (max && !d_expired) ||
-	    ((uintptr_t)d_expired & 7) || ((uintptr_t)d_workspace & 15) || ((uintptr_t)d_count & 3))
+	if (!t || (ts && !t->timed) || (flags & ~NSD_FLOW_EXPIRE_PAIRED) || !d_count || !d_workspace ||
+	    (max && !d_expired) || ((uintptr_t)d_expired & 7) || ((uintptr_t)d_workspace & 15) || ((uintptr_t)d_count & 3))
 		return NSD_ERR_ARG;
 	hipStream_t s = (hipStream_t)stream;
 	uint8_t *m = (uint8_t *)d_workspace;
 	const ExpWs w{ (ExpHdr *)m, (uint64_t *)(m + EXP_HDR), t->tab.slots };
 	const dim3 grid(grid_for(t, t->tab.slots)), block(BLOCK);
+	uint64_t *out = (uint64_t *)d_expired;
 	hipLaunchKernelGGL(expire_init, dim3(1), block, 0, s, w);
-	hipLaunchKernelGGL(expire_split, grid, block, 0, s, t->tab, w, before, flags, (uint64_t *)d_expired, max);
+	if (ts)
+		hipLaunchKernelGGL(HIP_KERNEL_NAME(expire_split<true, true>), grid, block, 0, s, t->tab, w, before, flags, out,
+				   max);
+	else if (t->timed)
+		hipLaunchKernelGGL(HIP_KERNEL_NAME(expire_split<true, false>), grid, block, 0, s, t->tab, w, before, flags, out,
+				   max);
+	else
+		hipLaunchKernelGGL(HIP_KERNEL_NAME(expire_split<false, false>), grid, block, 0, s, t->tab, w, before, flags,
+				   out, max);
 	hipLaunchKernelGGL(expire_clear, grid, block, 0, s, t->tab, w, max, d_count);
-	hipLaunchKernelGGL(expire_reinsert, grid, block, 0, s, t->tab, w, max);
+	if (t->timed)
+		hipLaunchKernelGGL(expire_reinsert<true>, grid, block, 0, s, t->tab, w, max);
+	else
+		hipLaunchKernelGGL(expire_reinsert<false>, grid, block, 0, s, t->tab, w, max);
 	t->last = s;
 	return hip_ok(hipGetLastError(), "launch") ? NSD_OK : NSD_ERR_HIP;
 }
 
-long nsd_flow_expire_rows(nsd_flow_table *t, uint64_t before, uint32_t flags, uint32_t max,
-			  std::vector<nsd_flow> &rows, uint64_t *stats)
+extern "C" int nsd_flow_expire_device(nsd_flow_table *t, uint64_t before, uint32_t flags, nsd_flow *d_expired,
+				      uint32_t max, uint32_t *d_count, void *d_workspace, void *stream)
+{
+	return expire_device(t, before, flags, d_expired, max, d_count, d_workspace, stream, false);
+}
+
+extern "C" int nsd_flow_expire_device_ts(nsd_flow_table *t, uint64_t before_ns, uint32_t flags, nsd_flowt *d_expired,
+					 uint32_t max, uint32_t *d_count, void *d_workspace, void *stream)
+{
+	return expire_device(t, before_ns, flags, d_expired, max, d_count, d_workspace, stream, true);
+}
+
+template <class Row>
+static long expire_rows(nsd_flow_table *t, uint64_t before, uint32_t flags, uint32_t max, std::vector<Row> &rows,
+			uint64_t *stats)
 {
 	rows.clear();
-	if (!t || (flags & ~NSD_FLOW_EXPIRE_PAIRED))
+	if (!t || (with_times<Row>() && !t->timed) || (flags & ~NSD_FLOW_EXPIRE_PAIRED))
 		return NSD_ERR_ARG;
 	hipStream_t s = t->last;
 	uint64_t st[NSD_FLOW_NSTATS];
@@ -1174,22 +1397,22 @@ long nsd_flow_expire_rows(nsd_flow_table *t, uint64_t before, uint32_t flags, ui
 		return NSD_ERR_HIP;
 	// (no more rows than flows)
 	const uint32_t have = (uint32_t)st[NSD_FLOW_ST_FLOWS], want = max < have ? max : have;
-	const size_t o_rows = 256, o_ws = (o_rows + (size_t)want * sizeof(nsd_flow) + 255) & ~(size_t)255;
+	const size_t o_rows = 256, o_ws = (o_rows + (size_t)want * sizeof(Row) + 255) & ~(size_t)255;
 	uint8_t *d = nullptr;
 	if (!hip_ok(hipMalloc(&d, o_ws + nsd_flow_expire_workspace_bytes(t)), "hipMalloc"))
 		return NSD_ERR_NOMEM;
 	uint32_t *d_count = (uint32_t *)d;
-	nsd_flow *d_rows = (nsd_flow *)(d + o_rows);
+	Row *d_rows = (Row *)(d + o_rows);
 	uint32_t count[2] = { 0, 0 };
 	ExpHdr h{};
-	bool ok = nsd_flow_expire_device(t, before, flags, d_rows, want, d_count, d + o_ws, s) == NSD_OK &&
+	bool ok = expire_device(t, before, flags, d_rows, want, d_count, d + o_ws, s, with_times<Row>()) == NSD_OK &&
 		  hip_ok(hipMemcpyAsync(count, d_count, 8, hipMemcpyDeviceToHost, s), "D2H") &&
 		  hip_ok(hipMemcpyAsync(&h, d + o_ws, sizeof(h), hipMemcpyDeviceToHost, s), "D2H") &&
 		  hip_ok(hipMemcpyAsync(st, t->tab.stats, sizeof(st), hipMemcpyDeviceToHost, s), "D2H") &&
 		  hip_ok(hipStreamSynchronize(s), "sync") && count[0] <= want;
 	if (ok && count[0]) {
 		rows.resize(count[0]);
-		ok = hip_ok(hipMemcpy(rows.data(), d_rows, (size_t)count[0] * sizeof(nsd_flow), hipMemcpyDeviceToHost), "D2H");
+		ok = hip_ok(hipMemcpy(rows.data(), d_rows, (size_t)count[0] * sizeof(Row), hipMemcpyDeviceToHost), "D2H");
 	}
 	(void)hipFree(d);
 	// every flow of before either left as a row or is back in the table
@@ -1203,16 +1426,40 @@ long nsd_flow_expire_rows(nsd_flow_table *t, uint64_t before, uint32_t flags, ui
 	return (long)count[1];
 }
 
-extern "C" long nsd_flow_expire(nsd_flow_table *t, uint64_t before, uint32_t flags, nsd_flow *expired, uint32_t max,
-				uint64_t *stats)
+long nsd_flow_expire_rows(nsd_flow_table *t, uint64_t before, uint32_t flags, uint32_t max,
+			  std::vector<nsd_flow> &rows, uint64_t *stats)
+{
+	return expire_rows(t, before, flags, max, rows, stats);
+}
+
+long nsd_flow_expire_rows_ts(nsd_flow_table *t, uint64_t before_ns, uint32_t flags, uint32_t max,
+			     std::vector<nsd_flowt> &rows, uint64_t *stats)
+{
+	return expire_rows(t, before_ns, flags, max, rows, stats);
+}
+
+template <class Row>
+static long expire_host(nsd_flow_table *t, uint64_t before, uint32_t flags, Row *expired, uint32_t max, uint64_t *stats)
 {
 	if (max && !expired)
 		return NSD_ERR_ARG;
-	std::vector<nsd_flow> rows;
-	const long q = nsd_flow_expire_rows(t, before, flags, max, rows, stats);
+	std::vector<Row> rows;
+	const long q = expire_rows(t, before, flags, max, rows, stats);
 	if (q >= 0 && !rows.empty())
-		memcpy(expired, rows.data(), rows.size() * sizeof(nsd_flow));
+		memcpy(expired, rows.data(), rows.size() * sizeof(Row));
 	return q;
+}
+
+extern "C" long nsd_flow_expire(nsd_flow_table *t, uint64_t before, uint32_t flags, nsd_flow *expired, uint32_t max,
+				uint64_t *stats)
+{
+	return expire_host(t, before, flags, expired, max, stats);
+}
+
+extern "C" long nsd_flow_expire_ts(nsd_flow_table *t, uint64_t before_ns, uint32_t flags, nsd_flowt *expired,
+				   uint32_t max, uint64_t *stats)
+{
+	return expire_host(t, before_ns, flags, expired, max, stats);
 }
 
 // ---- the same aggregation on the host -----------------------------------
@@ -1223,14 +1470,40 @@ struct KeyHash {
 struct KeyEq {
 	bool operator()(const Key &a, const Key &b) const { return key_eq(a, b); }
 };
+// the key bytes of a row (either row type begins with them)
+template <class Row>
+Key key_of(const Row &f)
+{
+	Key k;
+	memcpy(k.w, &f, 40);
+	k.w[4] &= 0x0000FFFFFFFFFFFFull;   // tcp_flags, rsvd
+	return k;
+}
+// the row of the reverse key: src / dst and sport / dport swapped
+template <class Row>
+Key reverse_of(const Row &f)
+{
+	Row r = f;
+	memcpy(r.src, f.dst, 16);
+	memcpy(r.dst, f.src, 16);
+	r.sport = f.dport;
+	r.dport = f.sport;
+	return key_of(r);
+}
+// what expires a row: its t_last where the rows carry times, else its `last`
+inline uint64_t idle_mark(const nsd_flow &f) { return f.last; }
+inline uint64_t idle_mark(const nsd_flowt &f) { return f.t_last; }
 } // namespace
 
-extern "C" long nsd_flow_cpu(const uint8_t *frames, const nsd_desc_t *desc, uint32_t n, const nsd_rec *rec,
-			     const uint32_t *ext, uint64_t base, nsd_flow *flows, uint32_t max, uint64_t *stats)
+// Row = nsd_flowt: ts[n], and each row's t_first / t_last = the smallest /
+// largest timestamp of its packets.
+template <class Row>
+static long flow_cpu(const uint8_t *frames, const nsd_desc_t *desc, uint32_t n, const nsd_rec *rec, const uint32_t *ext,
+		     const uint64_t *ts, uint64_t base, Row *flows, uint32_t max, uint64_t *stats)
 {
-	if (n > MAX_N || (n && (!frames || !desc || !rec)) || (max && !flows))
+	if (n > MAX_N || (n && (!frames || !desc || !rec || (with_times<Row>() && !ts))) || (max && !flows))
 		return NSD_ERR_ARG;
-	std::unordered_map<Key, nsd_flow, KeyHash, KeyEq> map;
+	std::unordered_map<Key, Row, KeyHash, KeyEq> map;
 	uint64_t st[NSD_FLOW_NSTATS] = { 0 };
 	for (uint32_t i = 0; i < n; i++) {
 		Key k;
@@ -1245,62 +1518,73 @@ extern "C" long nsd_flow_cpu(const uint8_t *frames, const nsd_desc_t *desc, uint
 		st[NSD_FLOW_ST_KEYED]++;
 		auto it = map.find(k);
 		if (it == map.end()) {
-			nsd_flow f;
+			Row f;
 			memset(&f, 0, sizeof(f));
 			memcpy(&f, k.w, 40);
 			f.first = base + i;
+			if constexpr (with_times<Row>())
+				f.t_first = UINT64_MAX;
 			it = map.emplace(k, f).first;
 		}
-		nsd_flow &f = it->second;
+		Row &f = it->second;
 		f.pkts++;
 		f.bytes += caplen;
 		f.last = base + i;
 		f.tcp_flags |= (uint8_t)tf;
+		if constexpr (with_times<Row>()) {
+			f.t_first = ts[i] < f.t_first ? ts[i] : f.t_first;
+			f.t_last = ts[i] > f.t_last ? ts[i] : f.t_last;
+		}
 	}
 	st[NSD_FLOW_ST_FLOWS] = map.size();
-	std::vector<nsd_flow> rows;
+	std::vector<Row> rows;
 	rows.reserve(map.size());
 	for (const auto &kv : map)
 		rows.push_back(kv.second);
 	sort_by_first(rows);
 	const size_t k = rows.size() < max ? rows.size() : max;
 	if (k)
-		memcpy(flows, rows.data(), k * sizeof(nsd_flow));
+		memcpy(flows, rows.data(), k * sizeof(Row));
 	if (stats)
 		memcpy(stats, st, sizeof(st));
 	return (long)rows.size();
 }
 
-// Flow rows (unique keys, any order) paired into conversations on the host:
-// a hash map from key to row, one lookup of the reverse per row.
-extern "C" long nsd_conv_cpu(const nsd_flow *flows, size_t n, int by, nsd_conv *conv, uint32_t max)
+extern "C" long nsd_flow_cpu(const uint8_t *frames, const nsd_desc_t *desc, uint32_t n, const nsd_rec *rec,
+			     const uint32_t *ext, uint64_t base, nsd_flow *flows, uint32_t max, uint64_t *stats)
 {
+	return flow_cpu(frames, desc, n, rec, ext, nullptr, base, flows, max, stats);
+}
+
+extern "C" long nsd_flow_cpu_ts(const uint8_t *frames, const nsd_desc_t *desc, uint32_t n, const nsd_rec *rec,
+				const uint32_t *ext, const uint64_t *ts, uint64_t base, nsd_flowt *flows, uint32_t max,
+				uint64_t *stats)
+{
+	return flow_cpu(frames, desc, n, rec, ext, ts, base, flows, max, stats);
+}
+
+// Flow rows (unique keys, any order) paired into conversations on the host:
+// a hash map from key to row, one lookup of the reverse per row.  Rows with
+// times give conversations with times: min / max over both directions.
+template <class Row, class Conv>
+static long conv_cpu(const Row *flows, size_t n, int by, Conv *conv, uint32_t max)
+{
+	static_assert(with_times<Row>() == with_times<Conv>(), "rows and conversations of one kind");
 	if (by < NSD_CONV_BY_FIRST || by > NSD_CONV_BY_PKTS || (n && !flows) || (max && !conv))
 		return NSD_ERR_ARG;
-	auto key_of = [](const nsd_flow &f) {
-		Key k;
-		memcpy(k.w, &f, 40);
-		k.w[4] &= 0x0000FFFFFFFFFFFFull;   // tcp_flags, rsvd
-		return k;
-	};
 	std::unordered_map<Key, size_t, KeyHash, KeyEq> map;
 	map.reserve(n);
 	for (size_t i = 0; i < n; i++)
 		map.emplace(key_of(flows[i]), i);
-	std::vector<nsd_conv> rows;
+	std::vector<Conv> rows;
 	for (size_t i = 0; i < n; i++) {
-		const nsd_flow &f = flows[i];
-		nsd_flow r = f;
-		memcpy(r.src, f.dst, 16);
-		memcpy(r.dst, f.src, 16);
-		r.sport = f.dport;
-		r.dport = f.sport;
-		const Key k = key_of(f), kr = key_of(r);
+		const Row &f = flows[i];
+		const Key k = key_of(f), kr = reverse_of(f);
 		const auto it = key_eq(k, kr) ? map.end() : map.find(kr);
-		const nsd_flow *g = it == map.end() ? nullptr : &flows[it->second];
+		const Row *g = it == map.end() ? nullptr : &flows[it->second];
 		if (g && (g->first < f.first || (g->first == f.first && memcmp(kr.w, k.w, 40) < 0)))
 			continue;   // the reverse is the originator: its row carries this one
-		nsd_conv c;
+		Conv c;
 		memset(&c, 0, sizeof(c));
 		memcpy(&c, k.w, 40);
 		c.tcp_flags_src = f.tcp_flags;
@@ -1308,36 +1592,50 @@ extern "C" long nsd_conv_cpu(const nsd_flow *flows, size_t n, int by, nsd_conv *
 		c.bytes_src = f.bytes;
 		c.first = f.first;
 		c.last = f.last;
+		if constexpr (with_times<Row>()) {
+			c.t_first = f.t_first;
+			c.t_last = f.t_last;
+		}
 		if (g) {
 			c.tcp_flags_dst = g->tcp_flags;
 			c.pkts_dst = g->pkts;
 			c.bytes_dst = g->bytes;
 			c.last = g->last > f.last ? g->last : f.last;
+			if constexpr (with_times<Row>()) {
+				c.t_first = g->t_first < f.t_first ? g->t_first : f.t_first;
+				c.t_last = g->t_last > f.t_last ? g->t_last : f.t_last;
+			}
 		}
 		rows.push_back(c);
 	}
 	sort_conv(rows, by);
 	const size_t k = rows.size() < max ? rows.size() : max;
 	if (k)
-		memcpy(conv, rows.data(), k * sizeof(nsd_conv));
+		memcpy(conv, rows.data(), k * sizeof(Conv));
 	return (long)rows.size();
+}
+
+extern "C" long nsd_conv_cpu(const nsd_flow *flows, size_t n, int by, nsd_conv *conv, uint32_t max)
+{
+	return conv_cpu(flows, n, by, conv, max);
+}
+
+extern "C" long nsd_conv_cpu_ts(const nsd_flowt *flows, size_t n, int by, nsd_convt *conv, uint32_t max)
+{
+	return conv_cpu(flows, n, by, conv, max);
 }
 
 // The expiry rules on the host over flow rows (unique keys, any order): a hash
 // map from key to row for the reverse lookup.  Survivors keep their input
 // order at the front of `flows`; the first `max` qualifying rows in input
-// order go to `expired`, the others stay.
-extern "C" long nsd_flow_expire_cpu(nsd_flow *flows, size_t n, uint64_t before, uint32_t flags, nsd_flow *expired,
-				    uint32_t max, size_t *remaining)
+// order go to `expired`, the others stay.  Rows with times expire by t_last
+// (idle_mark).
+template <class Row>
+static long expire_cpu(Row *flows, size_t n, uint64_t before, uint32_t flags, Row *expired, uint32_t max,
+		       size_t *remaining)
 {
 	if ((flags & ~NSD_FLOW_EXPIRE_PAIRED) || (n && !flows) || (max && !expired) || !remaining)
 		return NSD_ERR_ARG;
-	auto key_of = [](const nsd_flow &f) {
-		Key k;
-		memcpy(k.w, &f, 40);
-		k.w[4] &= 0x0000FFFFFFFFFFFFull;   // tcp_flags, rsvd
-		return k;
-	};
 	std::unordered_map<Key, size_t, KeyHash, KeyEq> map;
 	if (flags & NSD_FLOW_EXPIRE_PAIRED) {
 		map.reserve(n);
@@ -1347,19 +1645,14 @@ extern "C" long nsd_flow_expire_cpu(nsd_flow *flows, size_t n, uint64_t before, 
 	// decided over the rows as given, before any of them moves
 	std::vector<uint8_t> idle(n);
 	for (size_t i = 0; i < n; i++) {
-		const nsd_flow &f = flows[i];
-		idle[i] = f.last < before;
+		const Row &f = flows[i];
+		idle[i] = idle_mark(f) < before;
 		if (!idle[i] || !(flags & NSD_FLOW_EXPIRE_PAIRED))
 			continue;
-		nsd_flow r = f;
-		memcpy(r.src, f.dst, 16);
-		memcpy(r.dst, f.src, 16);
-		r.sport = f.dport;
-		r.dport = f.sport;
-		const Key k = key_of(f), kr = key_of(r);
+		const Key k = key_of(f), kr = reverse_of(f);
 		const auto it = key_eq(k, kr) ? map.end() : map.find(kr);
 		if (it != map.end())
-			idle[i] = flows[it->second].last < before;
+			idle[i] = idle_mark(flows[it->second]) < before;
 	}
 	size_t qualified = 0, kept = 0;
 	for (size_t i = 0; i < n; i++) {
@@ -1372,31 +1665,48 @@ extern "C" long nsd_flow_expire_cpu(nsd_flow *flows, size_t n, uint64_t before, 
 	return (long)qualified;
 }
 
+extern "C" long nsd_flow_expire_cpu(nsd_flow *flows, size_t n, uint64_t before, uint32_t flags, nsd_flow *expired,
+				    uint32_t max, size_t *remaining)
+{
+	return expire_cpu(flows, n, before, flags, expired, max, remaining);
+}
+
+extern "C" long nsd_flow_expire_cpu_ts(nsd_flowt *flows, size_t n, uint64_t before_ns, uint32_t flags,
+				       nsd_flowt *expired, uint32_t max, size_t *remaining)
+{
+	return expire_cpu(flows, n, before_ns, flags, expired, max, remaining);
+}
+
 // ---- host-memory entries --------------------------------------------------
 // Records made on the host (a record no batch carries, walked by the
 // per-packet path) into the table: n packets of `frames` with their records
-// and ext pool.  Synchronous.
+// and ext pool; ts[n] = their timestamps, for a timed table (else ignored).
+// Synchronous.
 extern "C" __attribute__((visibility("hidden"))) int nsd_flow_feed_records(nsd_flow_table *t, const uint8_t *frames,
 									    size_t frames_len, const nsd_desc_t *desc,
 									    uint32_t n, const nsd_rec *rec,
 									    const uint32_t *ext, uint32_t ext_words,
-									    uint64_t base)
+									    const uint64_t *ts, uint64_t base)
 {
 	if (!t || !n)
 		return t ? NSD_OK : NSD_ERR_ARG;
+	if (t->timed && !ts)
+		return NSD_ERR_ARG;
 	Stage &g = t->stage;
 	hipStream_t s = t->last;
 	if (!grow(g.frames, g.frames_cap, frames_len + NSD_FRAME_PAD) || !grow(g.desc, g.desc_cap, n) ||
-	    !grow(g.rec, g.rec_cap, n) || (ext_words && !grow(g.ext, g.ext_cap, ext_words)))
+	    !grow(g.rec, g.rec_cap, n) || (ext_words && !grow(g.ext, g.ext_cap, ext_words)) ||
+	    (t->timed && !grow(g.ts, g.ts_cap, n)))
 		return NSD_ERR_NOMEM;
 	bool ok = hip_ok(hipMemcpyAsync(g.frames, frames, frames_len, hipMemcpyHostToDevice, s), "H2D") &&
 		  hip_ok(hipMemsetAsync(g.frames + frames_len, 0, NSD_FRAME_PAD, s), "memset") &&
 		  hip_ok(hipMemcpyAsync(g.desc, desc, (size_t)n * 8, hipMemcpyHostToDevice, s), "H2D") &&
 		  hip_ok(hipMemcpyAsync(g.rec, rec, (size_t)n * sizeof(nsd_rec), hipMemcpyHostToDevice, s), "H2D") &&
-		  (!ext_words || hip_ok(hipMemcpyAsync(g.ext, ext, (size_t)ext_words * 4, hipMemcpyHostToDevice, s), "H2D"));
+		  (!ext_words || hip_ok(hipMemcpyAsync(g.ext, ext, (size_t)ext_words * 4, hipMemcpyHostToDevice, s), "H2D")) &&
+		  (!t->timed || hip_ok(hipMemcpyAsync(g.ts, ts, (size_t)n * 8, hipMemcpyHostToDevice, s), "H2D"));
 	if (!ok)
 		return NSD_ERR_HIP;
-	const int rc = nsd_flow_update_device(t, g.frames, g.desc, n, g.rec, g.ext, ext_words, base, s);
+	const int rc = update_device(t, g.frames, g.desc, n, g.rec, g.ext, ext_words, g.ts, t->timed, base, s);
 	if (rc != NSD_OK)
 		return rc;
 	return hip_ok(hipStreamSynchronize(s), "sync") ? NSD_OK : NSD_ERR_HIP;
@@ -1406,14 +1716,20 @@ extern "C" __attribute__((visibility("hidden"))) int nsd_flow_feed_records(nsd_f
 // program (accepted descriptors packed on the device, nsd_bpf_filter_device),
 // walked and accumulated, in chunks whose ext pool stays small.  The packets
 // fed get base, base + 1, ...  Returns their number or a negative NSD_ERR_*.
+// A timed table takes ts[n], the packets' timestamps (else ignored): those of
+// the accepted packets are packed on the host by the verdicts, as the sll
+// entries are, and *ts_max (may be NULL) is raised to the largest one fed.
 // Synchronous.
 extern "C" __attribute__((visibility("hidden"))) long nsd_flow_feed_host(nsd_flow_table *t, const uint8_t *frames,
 									  size_t frames_len, const nsd_desc_t *desc,
 									  const nsd_sll_t *sll, uint32_t n, int linktype,
-									  int mode, const nsd_bpf_prog *filter, uint64_t base)
+									  int mode, const nsd_bpf_prog *filter, const uint64_t *ts,
+									  uint64_t *ts_max, uint64_t base)
 {
-	if (!t || mode < PRINT_NORM || mode > PRINT_NONE || (n && (!frames || !desc)))
+	if (!t || mode < PRINT_NORM || mode > PRINT_NONE || (n && (!frames || !desc || (t->timed && !ts))))
 		return NSD_ERR_ARG;
+	if (!t->timed)
+		ts = nullptr;
 	if (n == 0)
 		return 0;
 	for (uint32_t i = 0; i < n; i++) {
@@ -1430,7 +1746,7 @@ extern "C" __attribute__((visibility("hidden"))) long nsd_flow_feed_host(nsd_flo
 	if (!grow(g.frames, g.frames_cap, frames_len + NSD_FRAME_PAD) || !grow(g.desc, g.desc_cap, most) ||
 	    !grow(g.rec, g.rec_cap, most) || !grow(g.ext, g.ext_cap, ext_words) ||
 	    !grow(g.ws, g.ws_cap, nsd_workspace_bytes(most)) || !grow(g.misc, g.misc_cap, 128 + NSD_NCOUNTERS * 8) ||
-	    (sll && !grow(g.sll, g.sll_cap, most)) ||
+	    (sll && !grow(g.sll, g.sll_cap, most)) || (ts && !grow(g.ts, g.ts_cap, most)) ||
 	    (filter && (!grow(g.desc_out, g.desc_out_cap, most) || !grow(g.verdict, g.verdict_cap, most) ||
 			!grow(g.bpf_ws, g.bpf_ws_cap, nsd_bpf_workspace_bytes(most)))))
 		return NSD_ERR_NOMEM;
@@ -1441,12 +1757,14 @@ extern "C" __attribute__((visibility("hidden"))) long nsd_flow_feed_host(nsd_flo
 		return NSD_ERR_HIP;
 	std::vector<uint32_t> verdict;
 	std::vector<nsd_sll_t> kept;
+	std::vector<uint64_t> kept_ts;
 	uint64_t fed = 0;
 	for (uint32_t a = 0; a < n; a += CHUNK) {
 		const uint32_t m = n - a < CHUNK ? n - a : CHUNK;
 		uint32_t m2 = m;
 		const uint64_t *use = g.desc;
 		const nsd_sll_t *use_sll = sll ? sll + a : nullptr;
+		const uint64_t *use_ts = ts ? ts + a : nullptr;
 		if (!hip_ok(hipMemcpyAsync(g.desc, desc + a, (size_t)m * 8, hipMemcpyHostToDevice, s), "H2D"))
 			return NSD_ERR_HIP;
 		if (filter) {
@@ -1458,23 +1776,37 @@ extern "C" __attribute__((visibility("hidden"))) long nsd_flow_feed_host(nsd_flo
 			    !hip_ok(hipStreamSynchronize(s), "sync") || m2 > m)
 				return NSD_ERR_HIP;
 			use = g.desc_out;
-			if (sll && m2) {
-				// the accepted packets' sockaddr_ll, packed like their descriptors
+			if ((sll || ts) && m2) {
+				// the accepted packets' sockaddr_ll and timestamps, packed like their descriptors
 				verdict.resize(m);
 				if (!hip_ok(hipMemcpy(verdict.data(), g.verdict, (size_t)m * 4, hipMemcpyDeviceToHost), "D2H"))
 					return NSD_ERR_HIP;
 				kept.clear();
-				for (uint32_t j = 0; j < m; j++)
-					if (verdict[j])
+				kept_ts.clear();
+				uint32_t passed = 0;
+				for (uint32_t j = 0; j < m; j++) {
+					if (!verdict[j])
+						continue;
+					passed++;
+					if (sll)
 						kept.push_back(sll[a + j]);
-				if (kept.size() != m2)
+					if (ts)
+						kept_ts.push_back(ts[a + j]);
+				}
+				if (passed != m2)
 					return NSD_ERR_HIP;
-				use_sll = kept.data();
+				if (sll)
+					use_sll = kept.data();
+				if (ts)
+					use_ts = kept_ts.data();
 			}
 		}
 		if (!m2)
 			continue;
+		if (use_ts && ts_max)
+			*ts_max = std::max(*ts_max, *std::max_element(use_ts, use_ts + m2));
 		bool ok = hip_ok(hipMemsetAsync(g.misc, 0, 128 + NSD_NCOUNTERS * 8, s), "memset") &&
+			  (!use_ts || hip_ok(hipMemcpyAsync(g.ts, use_ts, (size_t)m2 * 8, hipMemcpyHostToDevice, s), "H2D")) &&
 			  (!use_sll || hip_ok(hipMemcpyAsync(g.sll, use_sll, (size_t)m2 * sizeof(nsd_sll_t),
 							     hipMemcpyHostToDevice, s), "H2D"));
 		if (!ok)
@@ -1482,8 +1814,8 @@ extern "C" __attribute__((visibility("hidden"))) long nsd_flow_feed_host(nsd_flo
 		int rc = nsd_dissect_device_sll(g.frames, (const nsd_desc_t *)use, use_sll ? g.sll : nullptr, m2, linktype,
 						mode, g.rec, g.ext, ext_words, d_ext_used, d_counters, g.ws, s);
 		if (rc == NSD_OK)
-			rc = nsd_flow_update_device(t, g.frames, (const nsd_desc_t *)use, m2, g.rec, g.ext, ext_words,
-						    base + fed, s);
+			rc = update_device(t, g.frames, (const nsd_desc_t *)use, m2, g.rec, g.ext, ext_words, g.ts, t->timed,
+					   base + fed, s);
 		if (rc != NSD_OK)
 			return rc;
 		// (the chunk's buffers are reused by the next one)
@@ -1502,7 +1834,7 @@ extern "C" long nsd_flow_batch(const uint8_t *frames, size_t frames_len, const n
 	nsd_flow_table *t = nsd_flow_create(n ? n : 1);
 	if (!t)
 		return NSD_ERR_HIP;
-	long rc = nsd_flow_feed_host(t, frames, frames_len, desc, nullptr, n, linktype, mode, nullptr, 0);
+	long rc = nsd_flow_feed_host(t, frames, frames_len, desc, nullptr, n, linktype, mode, nullptr, nullptr, nullptr, 0);
 	if (rc >= 0)
 		rc = nsd_flow_export(t, flows, max, stats);
 	nsd_flow_destroy(t);

@@ -82,17 +82,23 @@ NSD_HIDDEN int nsd_start_for(int linktype);
 // than the current one (nsd_pipe.cpp)
 extern "C" NSD_HIDDEN int nsd_pipe_retarget(nsd_pipe *p, int linktype, int mode);
 
-// the flow table's feeds of host batches (nsd_flow.hip)
+// the flow table's feeds of host batches (nsd_flow.hip).  ts: the packets'
+// timestamps, read for a timed table only (where it must be given); *ts_max
+// (may be NULL) is raised to the largest timestamp among the packets fed
 extern "C" NSD_HIDDEN long nsd_flow_feed_host(nsd_flow_table *t, const uint8_t *frames, size_t frames_len,
 					      const nsd_desc_t *desc, const nsd_sll_t *sll, uint32_t n, int linktype,
-					      int mode, const nsd_bpf_prog *filter, uint64_t base);
+					      int mode, const nsd_bpf_prog *filter, const uint64_t *ts, uint64_t *ts_max,
+					      uint64_t base);
 extern "C" NSD_HIDDEN int nsd_flow_feed_records(nsd_flow_table *t, const uint8_t *frames, size_t frames_len,
 						const nsd_desc_t *desc, uint32_t n, const nsd_rec *rec,
-						const uint32_t *ext, uint32_t ext_words, uint64_t base);
-// nsd_flow_expire with room for every flow: the removed rows, sorted by
-// `first`, into `rows` (nsd_flow.hip; the capture-file loop's, nsd_replay.cpp)
+						const uint32_t *ext, uint32_t ext_words, const uint64_t *ts, uint64_t base);
+// nsd_flow_expire / nsd_flow_expire_ts with room for every flow: the removed
+// rows, sorted by `first`, into `rows` (nsd_flow.hip; the capture-file loop's,
+// nsd_replay.cpp)
 NSD_HIDDEN long nsd_flow_expire_rows(nsd_flow_table *t, uint64_t before, uint32_t flags, uint32_t max,
 				     std::vector<nsd_flow> &rows, uint64_t *stats);
+NSD_HIDDEN long nsd_flow_expire_rows_ts(nsd_flow_table *t, uint64_t before_ns, uint32_t flags, uint32_t max,
+					std::vector<nsd_flowt> &rows, uint64_t *stats);
 
 // what dissector_cleanup_all (nsd_proto.cpp) lets go of: the interface name
 // cache (nsd_format.cpp; each replay resets it too), the replay's cached

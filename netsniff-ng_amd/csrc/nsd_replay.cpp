@@ -99,10 +99,25 @@ long read_big(nsd_pcap *p, const nsd_bpf_prog *filter, std::vector<uint8_t> &fra
 // record no batch carries is filtered and walked by the per-packet path over
 // its first NSD_MAX_CAPLEN bytes and added with its whole caplen.
 // Batches carry at most `every` records; after each one fed (a record no
-// batch carries is a batch of its own) `after(fed)` runs when given, and a
-// negative return of it ends the loop with that status.
+// batch carries is a batch of its own) `after(fed, now)` runs, and a negative
+// return of it ends the loop with that status.  A timed table is fed the
+// records' timestamps (the reader's ts_ns), and now = the largest one among
+// the packets fed so far (0 for a plain table).
 namespace {
 constexpr uint32_t FLOWS_MAX_N = 1u << 16;
+
+// read_batch's ts_ns of one record header as stored (the record read_one gave)
+uint64_t record_ts_ns(const nsd_pcap *p, const uint8_t *rhdr)
+{
+	uint32_t sec, frac;
+	memcpy(&sec, rhdr, 4);
+	memcpy(&frac, rhdr + 4, 4);
+	if (p->swapped) {
+		sec = __builtin_bswap32(sec);
+		frac = __builtin_bswap32(frac);
+	}
+	return (uint64_t)sec * 1000000000ull + (p->nsec ? frac : (uint64_t)frac * 1000ull);
+}
 
 template <class After>
 long pcap_flows_loop(const char *path, int mode, const nsd_bpf_prog *filter, nsd_flow_table *t, uint32_t every,
@@ -114,27 +129,29 @@ long pcap_flows_loop(const char *path, int mode, const nsd_bpf_prog *filter, nsd
 	if (!p)
 		return NSD_ERR_ARG;
 	const int lt = (int)p->linktype;
-	const bool ll_used = has_ll(p);
+	const bool ll_used = has_ll(p), timed = nsd_flow_is_timed(t) != 0;
 	constexpr size_t CAP = 16u << 20;
 	std::vector<uint8_t> frames(CAP), big;
 	std::vector<nsd_desc_t> desc(every);
 	std::vector<nsd_sll_t> sll(every);
-	uint64_t fed = 0;
+	std::vector<uint64_t> ts(timed ? every : 0);
+	uint64_t fed = 0, now = 0;
 	long rc = NSD_OK;
 	while (rc == NSD_OK) {
-		const long n = read_batch(p, frames.data(), CAP, desc.data(), sll.data(), nullptr, every, nullptr, nullptr,
-					  nullptr);
+		const long n = read_batch(p, frames.data(), CAP, desc.data(), sll.data(), nullptr, every, nullptr,
+					  timed ? ts.data() : nullptr, nullptr);
 		if (n == 0)
 			break;
 		if (n > 0) {
 			const long k = nsd_flow_feed_host(t, frames.data(), batch_extent(desc.data(), (size_t)n), desc.data(),
-							  ll_used ? sll.data() : nullptr, (uint32_t)n, lt, mode, filter, fed);
+							  ll_used ? sll.data() : nullptr, (uint32_t)n, lt, mode, filter,
+							  timed ? ts.data() : nullptr, &now, fed);
 			if (k < 0)
 				rc = k;
 			else
 				fed += (uint64_t)k;
 			if (rc == NSD_OK)
-				rc = after(fed);
+				rc = after(fed, now);
 			continue;
 		}
 		if (n != NSD_ERR_CAPLEN) {
@@ -143,7 +160,8 @@ long pcap_flows_loop(const char *path, int mode, const nsd_bpf_prog *filter, nsd
 		}
 		nsd_sll_t ll;
 		bool pass;
-		const long caplen = read_big(p, filter, big, &ll, nullptr, nullptr, &pass);
+		uint8_t rhdr[32];
+		const long caplen = read_big(p, filter, big, &ll, nullptr, rhdr, &pass);
 		if (caplen <= 0) {
 			rc = caplen < 0 ? caplen : NSD_OK;
 			break;
@@ -156,10 +174,15 @@ long pcap_flows_loop(const char *path, int mode, const nsd_bpf_prog *filter, nsd
 		uint32_t ext[NSD_EXT_WORDS(NSD_EXT_MAX_LAYERS)] = { 0 };
 		rc = nsd_walk_packet_cpu(big.data(), head, lt, mode, ll_used ? &ll : nullptr, &rec, ext,
 					 NSD_EXT_WORDS(NSD_EXT_MAX_LAYERS), nullptr);
+		const uint64_t big_ts = record_ts_ns(p, rhdr);
 		if (rc == NSD_OK)
-			rc = nsd_flow_feed_records(t, big.data(), head, &d, 1, &rec, ext, NSD_EXT_WORDS(NSD_EXT_MAX_LAYERS), fed);
-		if (rc == NSD_OK)
-			rc = after(++fed);
+			rc = nsd_flow_feed_records(t, big.data(), head, &d, 1, &rec, ext, NSD_EXT_WORDS(NSD_EXT_MAX_LAYERS),
+						   &big_ts, fed);
+		if (rc == NSD_OK) {
+			if (timed && big_ts > now)
+				now = big_ts;
+			rc = after(++fed, now);
+		}
 	}
 	nsd_pcap_close(p);
 	return rc == NSD_OK ? (long)fed : rc;
@@ -168,7 +191,7 @@ long pcap_flows_loop(const char *path, int mode, const nsd_bpf_prog *filter, nsd
 
 extern "C" long nsd_pcap_flows(const char *path, int mode, const nsd_bpf_prog *filter, nsd_flow_table *t)
 {
-	return pcap_flows_loop(path, mode, filter, t, FLOWS_MAX_N, [](uint64_t) { return (long)NSD_OK; });
+	return pcap_flows_loop(path, mode, filter, t, FLOWS_MAX_N, [](uint64_t, uint64_t) { return (long)NSD_OK; });
 }
 
 // The same loop with idle flows leaving between the batches (the header's
@@ -180,10 +203,32 @@ extern "C" long nsd_pcap_flows_expire(const char *path, int mode, const nsd_bpf_
 	if (!sink || (flags & ~NSD_FLOW_EXPIRE_PAIRED))
 		return NSD_ERR_ARG;
 	std::vector<nsd_flow> rows;
-	return pcap_flows_loop(path, mode, filter, t, every, [&](uint64_t fed) -> long {
+	return pcap_flows_loop(path, mode, filter, t, every, [&](uint64_t fed, uint64_t) -> long {
 		if (fed <= idle)
 			return NSD_OK;
 		const long q = nsd_flow_expire_rows(t, fed - idle, flags, UINT32_MAX, rows, nullptr);
+		if (q < 0)
+			return q;
+		if (!rows.empty() && sink(rows.data(), (uint32_t)rows.size(), user) != 0)
+			return NSD_ERR_ARG;
+		return NSD_OK;
+	});
+}
+
+// The same by time (the header's "flow times"): once the largest timestamp
+// fed exceeds idle_ns, the flows whose t_last lies more than idle_ns before it
+// go to `sink` with their times, sorted by `first`.
+extern "C" long nsd_pcap_flows_expire_ts(const char *path, int mode, const nsd_bpf_prog *filter, nsd_flow_table *t,
+					 uint32_t every, uint64_t idle_ns, uint32_t flags, nsd_flow_sink_ts sink,
+					 void *user)
+{
+	if (!sink || (flags & ~NSD_FLOW_EXPIRE_PAIRED) || !nsd_flow_is_timed(t))
+		return NSD_ERR_ARG;
+	std::vector<nsd_flowt> rows;
+	return pcap_flows_loop(path, mode, filter, t, every, [&](uint64_t, uint64_t now) -> long {
+		if (now <= idle_ns)
+			return NSD_OK;
+		const long q = nsd_flow_expire_rows_ts(t, now - idle_ns, flags, UINT32_MAX, rows, nullptr);
 		if (q < 0)
 			return q;
 		if (!rows.empty() && sink(rows.data(), (uint32_t)rows.size(), user) != 0)

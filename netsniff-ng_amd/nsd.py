@@ -131,7 +131,10 @@ ABI_SYMBOLS = ["dissector_init_all", "dissector_entry_point", "dissector_cleanup
                "nsd_flow_export", "nsd_flow_batch", "nsd_pcap_flows", "nsd_flow_cpu",
                "nsd_flow_conv_workspace_bytes", "nsd_flow_conv_device", "nsd_flow_conversations", "nsd_conv_cpu",
                "nsd_flow_expire_workspace_bytes", "nsd_flow_expire_device", "nsd_flow_expire", "nsd_flow_expire_cpu",
-               "nsd_pcap_flows_expire"]
+               "nsd_pcap_flows_expire", "nsd_flow_create_timed", "nsd_flow_is_timed", "nsd_flow_update_device_ts",
+               "nsd_flow_export_device_ts", "nsd_flow_export_ts", "nsd_flow_conv_device_ts",
+               "nsd_flow_conversations_ts", "nsd_flow_expire_device_ts", "nsd_flow_expire_ts", "nsd_flow_cpu_ts",
+               "nsd_conv_cpu_ts", "nsd_flow_expire_cpu_ts", "nsd_pcap_flows_expire_ts"]
 
 # struct sockaddr_ll (nsd_sll_t), one per packet for LINKTYPE_LINUX_SLL batches
 SLL_DTYPE = np.dtype([("family", "<u2"), ("protocol", ">u2"), ("ifindex", "<i4"), ("hatype", "<u2"),
@@ -160,6 +163,11 @@ CONV_DTYPE = np.dtype([("src", "u1", (16,)), ("dst", "u1", (16,)), ("sport", "<u
                        ("pkts_src", "<u8"), ("bytes_src", "<u8"), ("pkts_dst", "<u8"), ("bytes_dst", "<u8"),
                        ("first", "<u8"), ("last", "<u8")])
 CONV_BYTES = 88
+# nsd_flowt / nsd_convt: the rows of a timed table, nsd_flow / nsd_conv followed by t_first, t_last
+FLOWT_DTYPE = np.dtype(FLOW_DTYPE.descr + [("t_first", "<u8"), ("t_last", "<u8")])
+FLOWT_BYTES = 88
+CONVT_DTYPE = np.dtype(CONV_DTYPE.descr + [("t_first", "<u8"), ("t_last", "<u8")])
+CONVT_BYTES = 104
 CONV_BY_FIRST, CONV_BY_BYTES, CONV_BY_PKTS = range(3)
 
 _lib = None
@@ -307,6 +315,20 @@ def lib():
                 ("nsd_flow_expire", ctypes.c_long, [_vp, _u64, _u32, _vp, _u32, _vp]),
                 ("nsd_flow_expire_cpu", ctypes.c_long, [_vp, _sz, _u64, _u32, _vp, _u32, _vp]),
                 ("nsd_pcap_flows_expire", ctypes.c_long,
+                 [ctypes.c_char_p, _int, _vp, _vp, _u32, _u64, _u32, FLOW_SINK, _vp]),
+                ("nsd_flow_create_timed", _vp, [_u32]),
+                ("nsd_flow_is_timed", _int, [_vp]),
+                ("nsd_flow_update_device_ts", _int, [_vp, _vp, _vp, _u32, _vp, _vp, _u32, _vp, _u64, _vp]),
+                ("nsd_flow_export_device_ts", _int, [_vp, _vp, _u32, _vp, _vp, _vp]),
+                ("nsd_flow_export_ts", ctypes.c_long, [_vp, _vp, _u32, _vp]),
+                ("nsd_flow_conv_device_ts", _int, [_vp, _int, _u32, _vp, _vp, _vp, _vp]),
+                ("nsd_flow_conversations_ts", ctypes.c_long, [_vp, _int, _u32, _vp, _vp]),
+                ("nsd_flow_expire_device_ts", _int, [_vp, _u64, _u32, _vp, _u32, _vp, _vp, _vp]),
+                ("nsd_flow_expire_ts", ctypes.c_long, [_vp, _u64, _u32, _vp, _u32, _vp]),
+                ("nsd_flow_cpu_ts", ctypes.c_long, [_vp, _vp, _u32, _vp, _vp, _vp, _u64, _vp, _u32, _vp]),
+                ("nsd_conv_cpu_ts", ctypes.c_long, [_vp, _sz, _int, _vp, _u32]),
+                ("nsd_flow_expire_cpu_ts", ctypes.c_long, [_vp, _sz, _u64, _u32, _vp, _u32, _vp]),
+                ("nsd_pcap_flows_expire_ts", ctypes.c_long,
                  [ctypes.c_char_p, _int, _vp, _vp, _u32, _u64, _u32, FLOW_SINK, _vp]),
                 ("nsd_last_schedule", _int, [])):
             if hasattr(L, name):
@@ -755,11 +777,14 @@ class FlowTable:
     """A flow table on the current device (nsd_flow_create): slots = the power
     of two >= 2 * max_flows.  update() accumulates dissected batches (cuda
     tensors, as dissect_device returns them) on torch's current stream;
-    raises NsdError without a GPU."""
+    raises NsdError without a GPU.  timed=True: nsd_flow_create_timed, a table
+    that also keeps each flow's smallest / largest capture timestamp (update
+    then takes ts; the *_ts methods give rows with t_first / t_last)."""
 
-    def __init__(self, max_flows):
+    def __init__(self, max_flows, timed=False):
         self.L = lib()
-        self.h = self.L.nsd_flow_create(max_flows)
+        self.timed = bool(timed)
+        self.h = (self.L.nsd_flow_create_timed if timed else self.L.nsd_flow_create)(max_flows)
         if not self.h:
             raise NsdError("nsd_flow_create failed (bad size, no memory or no GPU)")
         self.slots = self.L.nsd_flow_slots(self.h)
@@ -774,12 +799,20 @@ class FlowTable:
     def reset(self, stream=None):
         _check(self.L.nsd_flow_reset(self.h, self._stream(stream)), "nsd_flow_reset")
 
-    def update(self, frames, desc, rec, ext=None, base=0, n=None, stream=None):
+    def update(self, frames, desc, rec, ext=None, base=0, n=None, stream=None, ts=None):
         """One dissected batch: frames / desc as given to the walk, rec u8[n*16]
         and ext (the pool, or None) as it returned them; packet i counts as
-        base + i.  n: the packets of desc to take (default all)."""
+        base + i.  n: the packets of desc to take (default all).  ts: i64[n]
+        cuda tensor holding packet i's u64 timestamp (nsd_flow_update_device_ts;
+        a timed table needs it, a plain one refuses it)."""
         n = desc.numel() if n is None else n
         words = 0 if ext is None else ext.numel()
+        if ts is not None:
+            rc = self.L.nsd_flow_update_device_ts(self.h, frames.data_ptr(), desc.data_ptr(), n, rec.data_ptr(),
+                                                  None if ext is None else ext.data_ptr(), words, ts.data_ptr(), base,
+                                                  self._stream(stream, desc.device))
+            _check(rc, "nsd_flow_update_device_ts")
+            return
         rc = self.L.nsd_flow_update_device(self.h, frames.data_ptr(), desc.data_ptr(), n, rec.data_ptr(),
                                            None if ext is None else ext.data_ptr(), words, base,
                                            self._stream(stream, desc.device))
@@ -875,6 +908,88 @@ class FlowTable:
         _check(0 if n >= 0 else n, "nsd_flow_expire")
         return flows[:min(n, cap)], n, stats
 
+    # ---- the same with times (a timed table; NsdError on a plain one) ----
+    def export_device_ts(self, max_flows=None, flows=None, count=None, stats=None, stream=None):
+        """export_device with FLOWT_DTYPE rows (flows u8[max*88])."""
+        import torch
+        if flows is None:
+            flows = torch.empty((self.slots if max_flows is None else max_flows) * FLOWT_BYTES, dtype=torch.uint8,
+                                device="cuda")
+        if max_flows is None:
+            max_flows = flows.numel() // FLOWT_BYTES
+        if count is None:
+            count = torch.zeros(1, dtype=torch.int32, device=flows.device)
+        if stats is None:
+            stats = torch.zeros(FLOW_NSTATS, dtype=torch.int64, device=flows.device)
+        rc = self.L.nsd_flow_export_device_ts(self.h, flows.data_ptr(), max_flows, count.data_ptr(), stats.data_ptr(),
+                                              self._stream(stream, flows.device))
+        _check(rc, "nsd_flow_export_device_ts")
+        return flows, count, stats
+
+    def export_ts(self, max_flows=None):
+        """export with FLOWT_DTYPE rows."""
+        cap = self.slots if max_flows is None else max_flows
+        flows = np.zeros(max(cap, 1), dtype=FLOWT_DTYPE)
+        stats = np.zeros(FLOW_NSTATS, dtype=np.uint64)
+        n = self.L.nsd_flow_export_ts(self.h, flows.ctypes.data, cap, stats.ctypes.data)
+        _check(0 if n >= 0 else n, "nsd_flow_export_ts")
+        return flows[:min(n, cap)], stats
+
+    def conversations_device_ts(self, by, k, conv=None, count=None, workspace=None, stream=None):
+        """conversations_device with CONVT_DTYPE rows (conv u8[k*104])."""
+        import torch
+        if k is None:
+            k = 0xFFFFFFFF
+        if conv is None:
+            conv = torch.empty(min(k, self.slots) * CONVT_BYTES, dtype=torch.uint8, device="cuda")
+        if count is None:
+            count = torch.zeros(2, dtype=torch.int32, device=conv.device)
+        if workspace is None:
+            workspace = torch.empty(self.L.nsd_flow_conv_workspace_bytes(self.h), dtype=torch.uint8,
+                                    device=conv.device)
+        rc = self.L.nsd_flow_conv_device_ts(self.h, by, k, conv.data_ptr(), count.data_ptr(), workspace.data_ptr(),
+                                            self._stream(stream, conv.device))
+        _check(rc, "nsd_flow_conv_device_ts")
+        return conv, count
+
+    def conversations_ts(self, by=CONV_BY_BYTES, k=None):
+        """conversations with CONVT_DTYPE rows."""
+        cap = self.slots if k is None else min(k, self.slots)
+        conv = np.zeros(max(cap, 1), dtype=CONVT_DTYPE)
+        stats = np.zeros(FLOW_NSTATS, dtype=np.uint64)
+        n = self.L.nsd_flow_conversations_ts(self.h, by, cap, conv.ctypes.data, stats.ctypes.data)
+        _check(0 if n >= 0 else n, "nsd_flow_conversations_ts")
+        return conv[:min(n, cap)], stats
+
+    def expire_device_ts(self, before_ns, flags=0, max_flows=None, flows=None, count=None, workspace=None,
+                         stream=None):
+        """expire_device by time: the flows with t_last < before_ns leave as
+        FLOWT_DTYPE rows (flows u8[max*88])."""
+        import torch
+        if flows is None:
+            flows = torch.empty((self.slots if max_flows is None else max_flows) * FLOWT_BYTES, dtype=torch.uint8,
+                                device="cuda")
+        if max_flows is None:
+            max_flows = flows.numel() // FLOWT_BYTES
+        if count is None:
+            count = torch.zeros(2, dtype=torch.int32, device=flows.device)
+        if workspace is None:
+            workspace = torch.empty(self.L.nsd_flow_expire_workspace_bytes(self.h), dtype=torch.uint8,
+                                    device=flows.device)
+        rc = self.L.nsd_flow_expire_device_ts(self.h, before_ns, flags, flows.data_ptr(), max_flows, count.data_ptr(),
+                                              workspace.data_ptr(), self._stream(stream, flows.device))
+        _check(rc, "nsd_flow_expire_device_ts")
+        return flows, count
+
+    def expire_ts(self, before_ns, flags=0, max_flows=None):
+        """expire by time, FLOWT_DTYPE rows."""
+        cap = self.slots if max_flows is None else max_flows
+        flows = np.zeros(max(cap, 1), dtype=FLOWT_DTYPE)
+        stats = np.zeros(FLOW_NSTATS, dtype=np.uint64)
+        n = self.L.nsd_flow_expire_ts(self.h, before_ns, flags, flows.ctypes.data, cap, stats.ctypes.data)
+        _check(0 if n >= 0 else n, "nsd_flow_expire_ts")
+        return flows[:min(n, cap)], n, stats
+
     def close(self):
         if getattr(self, "h", None):
             self.L.nsd_flow_destroy(self.h)
@@ -914,6 +1029,50 @@ def flow_cpu(frames, desc, rec, ext=None, base=0, max_flows=None):
                            stats.ctypes.data)
     _check(0 if n >= 0 else n, "nsd_flow_cpu")
     return flows[:min(n, cap)], stats
+
+
+def flow_cpu_ts(frames, desc, rec, ts, ext=None, base=0, max_flows=None):
+    """flow_cpu with ts[n], the packets' u64 timestamps (nsd_flow_cpu_ts):
+    (flows FLOWT_DTYPE sorted by `first`, stats u64[8])."""
+    frames = np.ascontiguousarray(frames, dtype=np.uint8)
+    desc = np.ascontiguousarray(desc, dtype=np.uint64)
+    rec = np.ascontiguousarray(rec, dtype=REC_DTYPE)
+    ts = np.ascontiguousarray(ts, dtype=np.uint64)
+    if len(ts) != len(desc):
+        raise ValueError("one timestamp per packet")
+    ext_keep = None if ext is None or len(ext) == 0 else np.ascontiguousarray(ext).view(np.uint32)
+    cap = len(desc) if max_flows is None else max_flows
+    flows = np.zeros(max(cap, 1), dtype=FLOWT_DTYPE)
+    stats = np.zeros(FLOW_NSTATS, dtype=np.uint64)
+    n = lib().nsd_flow_cpu_ts(frames.ctypes.data, desc.ctypes.data, len(desc), rec.ctypes.data,
+                              None if ext_keep is None else ext_keep.ctypes.data, ts.ctypes.data, base,
+                              flows.ctypes.data, cap, stats.ctypes.data)
+    _check(0 if n >= 0 else n, "nsd_flow_cpu_ts")
+    return flows[:min(n, cap)], stats
+
+
+def conv_cpu_ts(flows, by=CONV_BY_FIRST, max_conv=None):
+    """conv_cpu over FLOWT_DTYPE rows (nsd_conv_cpu_ts): CONVT_DTYPE rows,
+    t_first / t_last = min / max over both directions."""
+    flows = np.ascontiguousarray(flows, dtype=FLOWT_DTYPE)
+    cap = len(flows) if max_conv is None else max_conv
+    conv = np.zeros(max(cap, 1), dtype=CONVT_DTYPE)
+    n = lib().nsd_conv_cpu_ts(flows.ctypes.data, len(flows), by, conv.ctypes.data, cap)
+    _check(0 if n >= 0 else n, "nsd_conv_cpu_ts")
+    return conv[:min(n, cap)]
+
+
+def flow_expire_cpu_ts(flows, before_ns, flags=0, max_flows=None):
+    """flow_expire_cpu by time over FLOWT_DTYPE rows (nsd_flow_expire_cpu_ts):
+    a row qualifies when its t_last < before_ns."""
+    rest = np.array(flows, dtype=FLOWT_DTYPE, ndmin=1)     # (a copy: the call compacts it)
+    cap = len(rest) if max_flows is None else max_flows
+    expired = np.zeros(max(cap, 1), dtype=FLOWT_DTYPE)
+    remaining = ctypes.c_size_t(0)
+    n = lib().nsd_flow_expire_cpu_ts(rest.ctypes.data, len(rest), before_ns, flags, expired.ctypes.data, cap,
+                                     ctypes.byref(remaining))
+    _check(0 if n >= 0 else n, "nsd_flow_expire_cpu_ts")
+    return rest[:remaining.value], expired[:min(n, cap)], n
 
 
 def conv_cpu(flows, by=CONV_BY_FIRST, max_conv=None):
@@ -969,6 +1128,26 @@ def pcap_flows_expire(path, table, every, idle, flags=0, mode=PRINT_NORM, prog=N
     n = lib().nsd_pcap_flows_expire(os.fsencode(path), mode, prog.h if prog is not None else None, table.h, every, idle,
                                     flags, sink, None)
     _check(0 if n >= 0 else n, "nsd_pcap_flows_expire")
+    return n, calls
+
+
+def pcap_flows_expire_ts(path, table, every, idle_ns, flags=0, mode=PRINT_NORM, prog=None):
+    """pcap_flows_expire by time on a timed FlowTable
+    (nsd_pcap_flows_expire_ts): after each batch, once the largest timestamp
+    fed exceeds idle_ns, the flows whose t_last lies more than idle_ns before
+    it leave.  Returns (packets fed, [FLOWT_DTYPE rows of each expiry that
+    removed any, sorted by `first`])."""
+    calls = []
+
+    @FLOW_SINK
+    def sink(rows, n, user):
+        buf = ctypes.string_at(rows, n * FLOWT_BYTES)
+        calls.append(np.frombuffer(buf, dtype=FLOWT_DTYPE).copy())
+        return 0
+
+    n = lib().nsd_pcap_flows_expire_ts(os.fsencode(path), mode, prog.h if prog is not None else None, table.h, every,
+                                       idle_ns, flags, sink, None)
+    _check(0 if n >= 0 else n, "nsd_pcap_flows_expire_ts")
     return n, calls
 
 
