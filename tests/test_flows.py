@@ -36,14 +36,27 @@ def chain_of(rec, ext, i):
     return ids, [0] + [2 * int(r["off2"][k]) for k in range(nl - 1)]
 
 
-def model(frames, desc, rec, ext, base=0):
+def outside_pool(rec, ext, i, ext_words):
+    """The header's rule for a pool of ext_words words: an ext-form record
+    whose entry header, or whose layer words, end past the pool."""
+    r = rec[i]
+    if int(r["nflags"]) & 7 != 7:
+        return False
+    slot = int.from_bytes(bytes(r["off2"][:4]), "little")
+    if slot + 4 > ext_words:
+        return True
+    return slot + 4 + min(int(ext[slot + 1]) & 0xFFFF, 64) > ext_words
+
+
+def model(frames, desc, rec, ext, base=0, ext_words=None):
     """{key: [flags, pkts, bytes, first, last]} and the stats, by the rules of
-    the header; key = (src16, dst16, sport, dport, l3, l4)."""
+    the header; key = (src16, dst16, sport, dport, l3, l4).  ext_words: the
+    size of the pool given (default: it holds every entry)."""
     flows, st = {}, [0] * 8
     offs, caps = T.desc_off(desc), T.desc_caplen(desc)
     for i in range(len(desc)):
         st[ST_PKTS] += 1
-        if int(rec[i]["nflags"]) & 0x20:
+        if int(rec[i]["nflags"]) & 0x20 or (ext_words is not None and outside_pool(rec, ext, i, ext_words)):
             st[ST_SKIPPED] += 1
             continue
         pkt = bytes(frames[offs[i]:offs[i] + min(int(caps[i]), MAX_CAPLEN)])
@@ -136,11 +149,11 @@ def many_flows(n, nflows, lens=None):
 _cache = {}
 
 
-def cached(name, make):
+def cached(name, make, mode=T.PRINT_NORM):
     """(frames, desc, oracle rec, oracle ext, model flows, model stats), built once."""
     if name not in _cache:
         frames, desc = make()
-        rec, ext, _, _ = T.oracle_records(frames, desc)
+        rec, ext, _, _ = T.oracle_records(frames, desc, mode=mode)
         _cache[name] = (frames, desc, rec, ext) + model(frames, desc, rec, ext)
     return _cache[name]
 
