@@ -74,6 +74,11 @@ extern "C" int nsd_launch_dissect_sll(const uint8_t *d_frames, const uint64_t *d
 				      uint32_t ext_words, uint32_t *d_ext_used, uint64_t *d_counters, void *d_ws,
 				      int grid, hipStream_t stream);
 extern "C" size_t nsd_launch_workspace_bytes(uint32_t n);
+// the byte offsets and extents of everything a launch of n packets on a grid
+// of `blocks` keeps in the workspace (out[20]: see the definition), for tests
+extern "C" int nsd_launch_workspace_layout(uint32_t n, uint32_t blocks, int compact, uint64_t *out);
+// 1 when the current device's last launch ran the split kernel with a shared tail (tests)
+extern "C" int nsd_last_tail_shared(void);
 
 // ---- host paths ------------------------------------------------------------
 // linktype -> first ops (nsd_host.cpp)

@@ -88,6 +88,18 @@ constexpr int WAVES = BLOCK / 64;
 #ifndef NSD_SCHED_SAMPLE
 #define NSD_SCHED_SAMPLE 32        // launches on a device between two schedule samples (sched_plan)
 #endif
+#ifndef NSD_TAIL_DIV
+#define NSD_TAIL_DIV 2             // the fast kernel shares the last 1 / NSD_TAIL_DIV of its rounds at run time (0: none)
+#endif
+#ifndef NSD_TAIL_MIN_ROUNDS
+#define NSD_TAIL_MIN_ROUNDS 16     // rounds (a wave's share of tiles) below which every tile is static
+#endif
+#ifndef NSD_TAIL_HEAD_BLOCKS
+#define NSD_TAIL_HEAD_BLOCKS 16    // blocks per head of the shared tail (64 waves a head; at least 4: fast_tiles' liveness)
+#endif
+#ifndef NSD_TAIL_TRIES
+#define NSD_TAIL_TRIES 3u          // other heads a wave tries once its own is empty
+#endif
 #ifndef NSD_SMALL_FRAME
 #define NSD_SMALL_FRAME 128        // average frame bytes up to which a sampled batch counts as small frames
 #endif
@@ -1772,18 +1784,54 @@ __device__ __forceinline__ void plain_walk(const LSrc<true, WIN1> &s, uint32_t c
 	w.data = len >= hl ? 34 + hl : 34;
 }
 
+// The fast loop's tiles: a static front and a shared tail.  Wave gw of nw walks
+// tiles gw, gw + nw, ... below `tail0` exactly as a grid stride would (no
+// atomics, the batch swept front to back).  The tiles from tail0 on - the
+// last rounds of the grid stride - are handed out at run time, because the
+// waves do not end together (C2: the XCDs' waves end between 172 and 188 us
+// on average, and a launch lasts until the last).  A ticket is a pair of
+// adjacent tiles: head h of `nheads` hands out pairs h, h + nheads, ... of
+// the tail in ascending order, one returning atomic of lane 0 per ticket on
+// the head's own 128-byte line.  A block's home head is blockIdx.x % nheads
+// (blocks with equal blockIdx.x % 8 share an XCD, and nheads is a multiple
+// of 8 when there are 8 or more, so a head's pullers sit on one XCD).  A
+// wave whose head has run out moves on to the next head (the next XCD's),
+// NSD_TAIL_TRIES times at most, and stays there; it does not visit them all.
+// A ticket is asked when the one before is read, two tiles before its first
+// descriptor is due (ask / take, as walk_tiles: an atomic's answer takes 1 -
+// 3 us under streaming load, a tile 1.6; asked one tile ahead, C2 kept 1.5 %
+// of the 2.2).  The launcher makes the
+// front's rounds even.  The loop's control state is declared wave-uniform
+// (`uni`): hipcc takes threadIdx.x >> 6 for divergent, and then kept tile
+// numbers, list counts and the ticket's head and flags in vector registers,
+// which cost dissect_fast<PRINT_NORM, true> its last ones (2 spilled).
+// Room: a packet adds at most one entry to the wave's list (a deferral from
+// the front or an ICMPv4 remainder from the back), and a wave asks only while
+// the list has room for every packet of the five tiles it holds and the new
+// two; once it may not ask, or its heads are empty, it asks no more, so no
+// tile follows a missing one in its pipeline.  Liveness: a wave stopped for
+// room walks at least cap / 64 - 1 tiles, i.e. rounds + rounds / 5 - 1 (the
+// launcher's cap), which is rounds + 2 or more (rounds >= NSD_TAIL_MIN_ROUNDS
+// = 16); a head's home waves alone then hold more than the head's tiles (4
+// blocks a head or more), so while a head has tiles left one of its home
+// waves can still ask.  heads == nullptr: every tile is static.
 template <int MODE, bool CR>
 __device__ __forceinline__ void fast_tiles(FastShared &sh, const uint8_t *__restrict__ frames,
 					   const uint64_t *__restrict__ desc, uint32_t n, int start_id,
 					   void *__restrict__ rec, const uint32_t *__restrict__ sll, uint32_t *__restrict__ side,
-					   uint4 *__restrict__ list, uint32_t cap, uint32_t &ndef, uint32_t &nicmp)
+					   uint4 *__restrict__ list, uint32_t cap, uint32_t &ndef, uint32_t &nicmp,
+					   uint32_t *__restrict__ heads, uint32_t tail0, uint32_t nheads)
 {
 	constexpr int SW = 2;
 	const int lane = threadIdx.x & 63;
-	const int wv = threadIdx.x >> 6;
+	// (wave-uniform, and said so: hipcc takes threadIdx.x >> 6 for divergent and
+	// then keeps the loop's whole control state - tile numbers, list counts, the
+	// ticket's head and flags - in vector registers)
+	const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
 	const uint32_t stride = gridDim.x * BLOCK;
 	FlagCnt fc;
-	uint32_t base = blockIdx.x * BLOCK + wv * 64;
+	auto uni = [](uint32_t x) -> uint32_t { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); };
+	uint32_t base = uni(blockIdx.x * BLOCK + wv * 64);
 
 	if (MODE != PRINT_NORM && MODE != PRINT_LESS) {
 		// every process() is NULL: no chain (dissector.c:51-53)
@@ -1877,7 +1925,7 @@ __device__ __forceinline__ void fast_tiles(FastShared &sh, const uint8_t *__rest
 				st_b128(e, make_uint4(i, w.icmp_off | w.icmp_len << 16, part, 0));
 				st_b128(e + 1, make_uint4((uint32_t)d0, (uint32_t)(d0 >> 32), 0, 0));
 			}
-			nicmp += (uint32_t)__popcll(pm);
+			nicmp = uni(nicmp + (uint32_t)__popcll(pm));
 		}
 		// per-ops counts of the finished chains, grouped by chain word (as
 		// walk_tiles)
@@ -1947,34 +1995,133 @@ __device__ __forceinline__ void fast_tiles(FastShared &sh, const uint8_t *__rest
 								   ((uint32_t)(w.offA >> 48) & 0xFF) << 16 | (w.offB & 0xFF) << 24;
 				st_b128(e + 1, make_uint4((uint32_t)d0, (uint32_t)(d0 >> 32), offs, 0));
 			}
-			ndef += (uint32_t)__popcll(dm);
+			ndef = uni(ndef + (uint32_t)__popcll(dm));
 		}
 	};
 	// two tiles' chunks in flight while one is walked: two register sets that
 	// swap roles (the loop unrolled by two), descriptors three tiles ahead
-	uint64_t d0 = dsc(base), d1 = dsc(base + stride), d2 = dsc(base + 2 * stride);
+	// The wave's tiles in order: `base`, then b1 and b2 (n: none), then what
+	// step() gives - the static front's next tile, `nxt`, while it lies below
+	// `slim`, a ticket's after that.  (The launcher shares the tail only when
+	// the front has more than three rounds: base, b1 and b2 are static, and
+	// the first ticket is asked when the front's last tile is fetched.)
+	const uint32_t ntiles = (n + 63) / 64;
+	const uint32_t slim = heads ? tail0 * 64 : n;
+	uint32_t cur = heads ? blockIdx.x % nheads : 0, tries = nheads > 1 ? 0 : NSD_TAIL_TRIES;
+	bool more = heads != nullptr, asked = false;
+	uint32_t gv = 0;
+	auto draw = [&]() {
+		if (lane == 0) {
+			uint32_t z;
+			asm volatile("v_mov_b32 %0, 0" : "=v"(z));   // (keeps hipcc's atomic optimizer off: walk_tiles)
+			gv = atomicAdd(heads + 32 * cur + z, 1u);
+		}
+	};
+	auto ask = [&]() {
+		asked = more && ndef + nicmp + 64u * 7 <= cap;
+		more = asked;
+		if (asked)
+			draw();
+	};
+	uint32_t second = n;   // the other tile of the last ticket (n: none, or taken)
+	auto take = [&]() -> uint32_t {   // the asked ticket's first tile (n: none)
+		if (!asked)
+			return n;
+		asked = false;
+		// the ticket's first tile (32 bits do: a head counts from zero in every
+		// launch and gives fewer tickets than the batch has tiles plus one per
+		// wave that finds it empty; a tile is walked only when it is below ntiles)
+		auto tile_of = [&]() -> uint32_t {
+			const uint32_t k = (uint32_t)__builtin_amdgcn_readfirstlane((int)gv);
+			return tail0 + 2 * (cur + k * nheads);
+		};
+		// (the ticket asked two tiles ago is read here, outside the loop below:
+		// its wait counts the loads issued since and leaves them in flight)
+		uint32_t t = tile_of();
+		// this head is empty: on to the next one, at once (the wave is about to
+		// run dry; the room for the tiles is reserved already).  Nested tests,
+		// not a loop: hipcc folds a loop's ticket read into the one above and
+		// then waits for every load in flight at each ticket.
+		auto next = [&]() {
+			tries++;
+			cur = cur + 1 == nheads ? 0 : cur + 1;
+			draw();
+			t = tile_of();
+		};
+		static_assert(NSD_TAIL_TRIES == 3, "take(): one nested test per try");
+		if (t >= ntiles && tries < NSD_TAIL_TRIES) {
+			next();
+			if (t >= ntiles && tries < NSD_TAIL_TRIES) {
+				next();
+				if (t >= ntiles && tries < NSD_TAIL_TRIES)
+					next();
+			}
+		}
+		if (t >= ntiles) {
+			more = false;
+			return n;
+		}
+		// (the batch's last tile without a partner: no tile may follow the
+		// missing one in the pipeline, so the wave asks no more)
+		second = t + 1 < ntiles ? (t + 1) * 64 : n;
+		if (second == n)
+			more = false;
+		return t * 64;
+	};
+	uint32_t nxt = uni(base + 3 * stride);
+	// (a ticket is asked when the one before is read, two tiles before its
+	// first descriptor is due: an atomic's answer takes 1 - 3 us under
+	// streaming load, a tile 1.6)
+	auto step = [&]() -> uint32_t {
+		uint32_t b;
+		if (nxt < slim) {
+			b = nxt;
+			nxt = uni(nxt + stride);
+			if (nxt >= slim)
+				ask();
+		} else if (second < n) {
+			b = second;
+			second = n;
+		} else {
+			b = take();
+			ask();
+		}
+		return b;
+	};
+	uint32_t b1 = base + stride < slim ? base + stride : n, b2 = base + 2 * stride < slim ? base + 2 * stride : n;
+	uint64_t d0 = dsc(base), d1 = dsc(b1), d2 = dsc(b2);
 	Chunks<WIN1> chA, chB;
 	stage_load<WIN1, true>(chA, frames, d0, lane);
 	stage_load<WIN1, true>(chB, frames, d1, lane);
 	for (;;) {
-		uint64_t d3 = dsc(base + 3 * stride);
+		uint32_t b3 = uni(step());
+		uint64_t d3 = dsc(b3);
 		tile(chA, d0, d2);
 		d0 = d1;
 		d1 = d2;
 		d2 = d3;
-		base += stride;
+		base = uni(b1);
+		b1 = b2;
+		b2 = b3;
 		if (base >= n)
 			break;
-		d3 = dsc(base + 3 * stride);
+		b3 = uni(step());
+		d3 = dsc(b3);
 		tile(chB, d0, d2);
 		d0 = d1;
 		d1 = d2;
 		d2 = d3;
-		base += stride;
+		base = uni(b1);
+		b1 = b2;
+		b2 = b3;
 		if (base >= n)
 			break;
 	}
-	drain_stores();   // the loop's records, list entries and side words are complete
+	drain_stores();   // the loop's records, list entries and side words are complete (and its last ticket has come)
+	// the list held every entry (ask()'s room rule); a broken invariant
+	// overwrote the next wave's list: counted, as walk_tiles does
+	if (lane == 0 && ndef + nicmp > cap)
+		atomicAdd(&sh.cnt[NSD_CNT_LISTOVF], 1ull);
 	fc.flush(sh.cnt, lane);
 }
 
@@ -2174,7 +2321,7 @@ __global__ __launch_bounds__(BLOCK, CR ? NSD_FAST_MINW : NSD_FAST_MINW_FULL) voi
 	void *__restrict__ rec, unsigned long long *__restrict__ counters, uint4 *__restrict__ lists, uint32_t cap,
 	const uint32_t *__restrict__ sll, uint32_t *__restrict__ side, unsigned long long *__restrict__ sched,
 	uint32_t *__restrict__ ext, uint32_t ext_words, uint32_t *__restrict__ ext_used, uint32_t chunk,
-	uint64_t *__restrict__ pend, uint32_t region)
+	uint64_t *__restrict__ pend, uint32_t region, uint32_t *__restrict__ heads, uint32_t tail0, uint32_t nheads)
 {
 	constexpr int SW = 2;
 	union FastLds {
@@ -2190,7 +2337,7 @@ __global__ __launch_bounds__(BLOCK, CR ? NSD_FAST_MINW : NSD_FAST_MINW_FULL) voi
 	const uint32_t gw = blockIdx.x * WAVES + wv;
 	uint4 *const list = lists + (size_t)gw * cap * SW;   // this wave's
 	uint32_t ndef = 0, nicmp = 0;
-	fast_tiles<MODE, CR>(sh, frames, desc, n, start_id, rec, sll, side, list, cap, ndef, nicmp);
+	fast_tiles<MODE, CR>(sh, frames, desc, n, start_id, rec, sll, side, list, cap, ndef, nicmp, heads, tail0, nheads);
 	if (lane == 0) {
 		sh.pcnt[wv] = nicmp;
 		if (sched && ndef)
@@ -2208,7 +2355,19 @@ __global__ __launch_bounds__(BLOCK, CR ? NSD_FAST_MINW : NSD_FAST_MINW_FULL) voi
 	if constexpr (MODE == PRINT_NORM || MODE == PRINT_LESS) {
 		// (the barrier also orders the flush's LDS reads before the walker
 		// pool's set-up in the same words)
-		if (__syncthreads_or(ndef != 0)) {
+		const bool tail = __syncthreads_or(ndef != 0);
+		// The shared tail's heads belong to the library's counter set of this
+		// stream (tail_set) and are zero between launches: every block counts
+		// itself in the word after the heads once its waves have drawn their
+		// last ticket (the barrier above; fast_tiles waited for every ticket it
+		// asked; a block without a tile counts too), and the block that comes
+		// last zeroes the heads and that word.  Launches on one stream are
+		// ordered, so the next one finds zeros.
+		if (heads && threadIdx.x == 0 && atomicAdd(heads + 32 * nheads, 1u) == gridDim.x - 1) {
+			for (uint32_t h = 0; h <= nheads; h++)
+				atomicExch(heads + 32 * h, 0u);
+		}
+		if (tail) {
 			__shared__ uint32_t s_touch[64];
 			walk_lists<MODE, CR>(su.w, s_touch, frames, desc, n, rec, ext, ext_words, ext_used, chunk, counters,
 					     list, min(ndef, cap), pend, region);
@@ -2293,6 +2452,7 @@ struct Sched {
 	bool recorded = false;                 // the pending sample's event is recorded (sched_sampled)
 	bool discard = false;                  // the pending sample failed: wait for its copies, use nothing
 	int launches = 0, last = 0;
+	bool last_shared = false;              // the last launch's fast kernel shared its tail (nsd_last_tail_shared)
 	uint64_t sampled = 0;                  // packets of the sampled launch in flight
 	unsigned long long *host = nullptr;    // its pair, then its counters [32, 34) before and after
 	hipEvent_t ev = nullptr;
@@ -2319,6 +2479,7 @@ int cur_dev()
 struct Plan {
 	bool fused, sample, small, prio, ring;
 	int cus;
+	bool capturing;
 };
 Plan sched_plan(uint32_t n, unsigned long long *pair, const uint64_t *counters, hipStream_t stream)
 {
@@ -2331,12 +2492,13 @@ Plan sched_plan(uint32_t n, unsigned long long *pair, const uint64_t *counters, 
 			cus = 256;
 		S.cus = cus;
 	}
-	Plan p{ false, false, false, true, true, S.cus };
+	Plan p{ false, false, false, true, true, S.cus, false };
 	// a launch captured into a graph takes the schedule as it stands and is
 	// never the sample (an event query or a host copy would break the
 	// capture; the graph replays this plan)
 	hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
 	const bool capturing = hipStreamIsCapturing(stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
+	p.capturing = capturing;
 	// (a sample is read only once sched_sampled has recorded its event: between
 	// the plan and that record, the event still stands for an older sample, and
 	// another stream's launch must not take the copies in flight for it).
@@ -2380,6 +2542,53 @@ Plan sched_plan(uint32_t n, unsigned long long *pair, const uint64_t *counters, 
 	}
 	S.last = p.fused ? NSD_SCHED_FUSED : NSD_SCHED_SPLIT;
 	return p;
+}
+
+// The fast kernel's shared tail draws its tiles from heads that are zero
+// between launches (fast_tiles, dissect_fast).  They live in counter sets the
+// library owns, one per (device, stream), not in the caller's workspace: a
+// workspace comes as it is (torch.empty, the debug fill), and zeroing words of
+// it would cost a launch or a memset per batch.  A set is made on its
+// stream's first launch - zeroed once, on that stream - and never freed (as
+// Sched::host); the kernel leaves it zeroed, and launches on one stream are
+// ordered.  One 128-byte line per head, then the line of the blocks' count.
+// nullptr (the static loop): allocation failed, or NSD_TAIL_SETS streams have
+// one already.
+constexpr uint32_t NSD_TAIL_HEADS_MAX = 256;
+constexpr int NSD_TAIL_SETS = 64;
+struct TailSet {
+	int dev;
+	hipStream_t stream;
+	uint32_t *heads;
+};
+TailSet g_tail[NSD_TAIL_SETS];
+int g_ntail = 0;
+
+uint32_t *tail_set(hipStream_t stream)
+{
+	// (hipStreamPerThread names a different stream in every thread: no set)
+	if (stream == hipStreamPerThread)
+		return nullptr;
+	std::lock_guard<std::mutex> g(g_sched_mu);
+	const int dev = cur_dev();
+	for (int k = 0; k < g_ntail; k++)
+		if (g_tail[k].dev == dev && g_tail[k].stream == stream)
+			return g_tail[k].heads;
+	if (g_ntail == NSD_TAIL_SETS)
+		return nullptr;
+	const size_t bytes = (size_t)(NSD_TAIL_HEADS_MAX + 1) * 128;
+	uint32_t *h = nullptr;
+	if (hipMalloc((void **)&h, bytes) != hipSuccess) {
+		(void)hipGetLastError();
+		return nullptr;
+	}
+	if (hipMemsetAsync(h, 0, bytes, stream) != hipSuccess) {
+		(void)hipGetLastError();
+		(void)hipFree(h);
+		return nullptr;
+	}
+	g_tail[g_ntail++] = TailSet{ dev, stream, h };
+	return h;
 }
 
 // A failed sample (under the lock): copies queued for it may still be in
@@ -2456,6 +2665,15 @@ extern "C" int nsd_set_debug_fill(int byte)
 	return g_debug_fill.exchange(byte);
 }
 
+// 1 when the last launch on the current device ran dissect_fast with a shared
+// tail (tickets from a counter set), 0 when its tiles were static or it ran
+// the fused kernel (tests)
+extern "C" int nsd_last_tail_shared(void)
+{
+	std::lock_guard<std::mutex> g(g_sched_mu);
+	return g_sched[cur_dev()].last_shared ? 1 : 0;
+}
+
 extern "C" int nsd_last_schedule(void)
 {
 	std::lock_guard<std::mutex> g(g_sched_mu);
@@ -2466,6 +2684,8 @@ extern "C" int nsd_last_schedule(void)
 // schedule's fast lists (up to 32 bytes per slot), a region no kernel uses
 // (8 bytes per fast wave: the size callers allocate is kept) and its tail's
 // pending lists (u64 per slot, of the 16 bytes per packet slot kept there)
+// (fast_carve: with a shared tail both kinds of list hold a fifth more slots,
+// in the same bytes)
 static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 // (the last 256 bytes: the schedule sample's pair, at sched_pair_at)
 // (then the fused kernel's group tile counters: a 128-byte line per block
@@ -2482,6 +2702,111 @@ static size_t sched_pair_at(uint32_t n)
 extern "C" size_t nsd_launch_workspace_bytes(uint32_t n)
 {
 	return sched_pair_at(n) + 256;
+}
+
+// The split schedule's carve of the workspace for a grid of `fblocks`: per
+// wave a fast list of `cap` 32-byte slots (two uint4: fast_tiles) from the
+// start, then 8 unused bytes per list, then the tail's pending lists, `cap`
+// u64 per wave (a packet the tail walks adds at most one entry).  Static
+// tiles: cap is the wave's share, `rounds` tiles.  Shared tail: a wave may
+// walk more than its share, so cap is a fifth larger, in the same bytes -
+// the workspace keeps 32 + 16 bytes per slot before the tile counters
+// (gtiles_at) and the static carve uses 32 + 8 of them; 1.2 x (32 + 8) = 48.
+// ok: the carve ends at or before gtiles_at(n) (a grid near NSD_MAX_GRID can
+// miss it by the alignment; such a launch runs the static loop).
+struct FastCarve {
+	uint32_t rounds, cap;
+	size_t lists_bytes, pend_at, pend_bytes;
+	bool ok;
+};
+static FastCarve fast_carve(uint32_t n, uint32_t fblocks, bool shared)
+{
+	FastCarve c;
+	c.rounds = region_for(n, fblocks) / nsd::BLOCK;
+	c.cap = c.rounds * 64;
+	if (shared)
+		c.cap += c.cap / 5;
+	const size_t nlists = (size_t)fblocks * nsd::WAVES;
+	c.lists_bytes = 32 * nlists * c.cap;
+	c.pend_at = align256(c.lists_bytes) + align256(nlists * 8);
+	c.pend_bytes = 8 * nlists * c.cap;
+	c.ok = c.pend_at + c.pend_bytes <= gtiles_at(n);
+	return c;
+}
+// the shared tail of a launch of `rounds` rounds over `fblocks` blocks: the
+// rounds it shares (0: none) and its heads
+// fast_tiles' liveness: a wave stopped for room has walked rounds + rounds / 5
+// - 1 tiles or more, i.e. y + rounds / 5 - 1 of the tail's (y shared rounds, at
+// most rounds / 2 + 1), and a head's tiles are at most 17 / 16 of y per home
+// wave (16 blocks a head or more): y + rounds / 5 - 1 > y * 17 / 16 for every
+// rounds >= 16 while y <= rounds / 2 + 1
+static_assert(NSD_TAIL_DIV == 0 || (NSD_TAIL_DIV >= 2 && NSD_TAIL_MIN_ROUNDS >= 16 && NSD_TAIL_HEAD_BLOCKS >= 16),
+	      "fast_tiles: a static front of more than three rounds, and its liveness argument");
+static uint32_t tail_rounds_for(uint32_t rounds)
+{
+	if (NSD_TAIL_DIV == 0 || rounds < NSD_TAIL_MIN_ROUNDS)
+		return 0;
+	uint32_t t = rounds / NSD_TAIL_DIV;
+	if (!t)
+		t = 1;
+	// (an even front: a ticket's pair then falls on one turn of the unrolled loop)
+	return t + ((rounds - t) & 1);
+}
+static uint32_t tail_heads_for(uint32_t fblocks)
+{
+	uint32_t h = fblocks / NSD_TAIL_HEAD_BLOCKS;
+	if (h >= 8)
+		h &= ~7u;   // whole XCDs' worth: a head's blocks share blockIdx.x % 8
+	if (h > NSD_TAIL_HEADS_MAX)
+		h = NSD_TAIL_HEADS_MAX & ~7u;
+	return h ? h : 1;
+}
+
+// Where a launch of n packets on a grid of `blocks` (capped as the launcher
+// caps it: one block per 256 packets, NSD_MAX_GRID) puts what in the
+// workspace, as byte offsets and extents, for tests:
+//   out[0]      nsd_launch_workspace_bytes(n)
+//   out[1, 2]   the fused kernel's pending lists (8 bytes a slot)
+//   out[3, 4]   its tile counters (a 128-byte line per block; compact only: else extent 0)
+//   out[5, 6]   the schedule sample's pair
+//   out[7, 8]   the split schedule's fast lists, static tiles (32 bytes a slot)
+//   out[9, 10]  its tail's pending lists, static tiles
+//   out[11, 12] the fast lists with a shared tail
+//   out[13, 14] the pending lists with a shared tail
+//   out[15]     1 when the carve with a shared tail fits (else such a launch is static)
+//   out[16, 17] a wave's list slots, static and with a shared tail
+//   out[18, 19] the shared tail's rounds (0: the launch is static) and heads
+extern "C" int nsd_launch_workspace_layout(uint32_t n, uint32_t blocks, int compact, uint64_t *out)
+{
+	if (!n || !blocks || !out)
+		return NSD_ERR_ARG;
+	const uint32_t want = ((n + 63) / 64 + nsd::WAVES - 1) / nsd::WAVES;
+	if (blocks > NSD_MAX_GRID)
+		blocks = NSD_MAX_GRID;
+	if (blocks > want)
+		blocks = want;
+	const FastCarve st = fast_carve(n, blocks, false), sh = fast_carve(n, blocks, true);
+	out[0] = nsd_launch_workspace_bytes(n);
+	out[1] = 0;
+	out[2] = 8ull * region_for_fused(n, blocks, compact != 0) * blocks;
+	out[3] = gtiles_at(n);
+	out[4] = compact ? 128ull * blocks : 0;
+	out[5] = sched_pair_at(n);
+	out[6] = 16;
+	out[7] = 0;
+	out[8] = st.lists_bytes;
+	out[9] = st.pend_at;
+	out[10] = st.pend_bytes;
+	out[11] = 0;
+	out[12] = sh.lists_bytes;
+	out[13] = sh.pend_at;
+	out[14] = sh.pend_bytes;
+	out[15] = sh.ok;
+	out[16] = st.cap;
+	out[17] = sh.cap;
+	out[18] = sh.ok ? tail_rounds_for(st.rounds) : 0;
+	out[19] = tail_heads_for(blocks);
+	return 0;
 }
 
 extern "C" int nsd_launch_dissect(const uint8_t *d_frames, const uint64_t *d_desc, uint32_t n,
@@ -2603,6 +2928,10 @@ extern "C" int nsd_launch_dissect_rec(const uint8_t *d_frames, const uint64_t *d
 			if (!launched())
 				return -2;
 		}
+		{
+			std::lock_guard<std::mutex> g(g_sched_mu);
+			g_sched[cur_dev()].last_shared = false;
+		}
 		hipLaunchKernelGGL(f, dim3(blocks), dim3(BLOCK), 0, stream, d_frames, d_desc, n, start_id, d_rec, d_ext,
 				   ext_words, d_ext_used, chunk_for(blocks), (unsigned long long *)d_counters,
 				   (uint64_t *)d_ws, region_for_fused(n, blocks, compact), (const uint32_t *)d_sll, sched,
@@ -2610,7 +2939,7 @@ extern "C" int nsd_launch_dissect_rec(const uint8_t *d_frames, const uint64_t *d
 	} else {
 		typedef void (*ffn)(const uint8_t *, const uint64_t *, uint32_t, int, void *, unsigned long long *, uint4 *,
 				    uint32_t, const uint32_t *, uint32_t *, unsigned long long *, uint32_t *, uint32_t,
-				    uint32_t *, uint32_t, uint64_t *, uint32_t);
+				    uint32_t *, uint32_t, uint64_t *, uint32_t, uint32_t *, uint32_t, uint32_t);
 		static const ffn fast[2][3] = {
 			{ dissect_fast<PRINT_NORM, false>, dissect_fast<PRINT_LESS, false>, dissect_fast<PRINT_HEX, false> },
 			{ dissect_fast<PRINT_NORM, true>, dissect_fast<PRINT_LESS, true>, dissect_fast<PRINT_HEX, true> },
@@ -2628,19 +2957,31 @@ extern "C" int nsd_launch_dissect_rec(const uint8_t *d_frames, const uint64_t *d
 		if (fcap > NSD_MAX_GRID)
 			fcap = NSD_MAX_GRID;
 		const uint32_t fblocks = want < fcap ? want : fcap;
-		const uint32_t cap = region_for(n, fblocks) / WAVES;   // slots per fast wave
-		const uint32_t nlists = fblocks * WAVES;
-		const size_t slotb = 32;   // a list slot: two uint4 (fast_tiles)
+		// The last rounds' tiles handed out at run time (fast_tiles), when the
+		// launch has rounds enough, its lists fit a fifth larger (fast_carve)
+		// and the stream has a counter set; not in a capture (a graph replays
+		// its arguments on whatever stream it is launched into) and not for
+		// the modes without a chain.  Else every tile is static.
+		FastCarve cv = fast_carve(n, fblocks, true);
+		const uint32_t trounds = mi != 2 && !plan.capturing && cv.ok ? tail_rounds_for(cv.rounds) : 0;
+		uint32_t *const heads = trounds ? tail_set(stream) : nullptr;
+		if (!heads)
+			cv = fast_carve(n, fblocks, false);
+		{
+			std::lock_guard<std::mutex> g(g_sched_mu);
+			g_sched[cur_dev()].last_shared = heads != nullptr;
+		}
+		const uint32_t cap = cv.cap;   // slots per fast wave
+		const uint32_t nheads = tail_heads_for(fblocks);
+		const uint32_t tail0 = heads ? (cv.rounds - trounds) * fblocks * WAVES : 0;
 		uint8_t *ws = (uint8_t *)d_ws;
 		uint4 *lists = (uint4 *)ws;
-		// the tail's pending lists, `cap` u64 slots per wave (a packet the tail
-		// walks adds at most one entry), past 8 unused bytes per list
-		uint64_t *pend = (uint64_t *)(ws + align256(slotb * nlists * cap) + align256((size_t)nlists * 8));
+		uint64_t *pend = (uint64_t *)(ws + cv.pend_at);
 		// compact records: the pool's side words (when it has them), for leaf ends
 		uint32_t *side = compact && d_ext && ext_words >= n ? d_ext : nullptr;
 		hipLaunchKernelGGL(fast[ci][mi], dim3(fblocks), dim3(BLOCK), 0, stream, d_frames, d_desc, n, start_id,
 				   d_rec, (unsigned long long *)d_counters, lists, cap, (const uint32_t *)d_sll, side, sched,
-				   d_ext, ext_words, d_ext_used, chunk_for(fblocks), pend, cap * WAVES);
+				   d_ext, ext_words, d_ext_used, chunk_for(fblocks), pend, cap * WAVES, heads, tail0, nheads);
 	}
 	if (!launched())
 		return -2;

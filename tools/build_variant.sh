@@ -4,10 +4,12 @@
 # as -D flags; experiments that change code (e.g. skip a phase to time the
 # rest) are patches (paths csrc/...) applied to a scratch copy of the
 # sources, never switches in the product sources.  tools/variants/ keeps
-# icmp_queue.patch, nofasticmp.patch and noicmp.patch.
+# icmp_queue.patch, nofasticmp.patch, noicmp.patch and timeline.patch (per-wave
+# time stamps of dissect_fast, read by tools/kbench.py with KB_DBG=1).
 #   tools/build_variant.sh u8 -DNSD_CSUM_U=8
 #   PATCH=tools/variants/noicmp.patch tools/build_variant.sh noicmp
 #   REV=HEAD~1 tools/build_variant.sh prev        (a committed revision's kernels)
+#   PATCH=tools/variants/timeline.patch tools/build_variant.sh tl
 set -e
 cd "$(dirname "$0")/.."
 name=$1; shift
@@ -25,7 +27,7 @@ make -s -C netsniff-ng_amd
 H="/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function $*"
 $H -c $d/x/a/csrc/nsd_kernels.hip -o $d/k.o
 objs="$d/k.o"
-for f in nsd_bpf nsd_cpu nsd_host nsd_pipe nsd_format nsd_lookup nsd_pcap nsd_proto; do
+for f in nsd_bpf nsd_cpu nsd_host nsd_pipe nsd_format nsd_lookup nsd_pcap nsd_replay nsd_proto nsd_flow; do
   objs="$objs netsniff-ng_amd/build/$f.o"
 done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $d/libnsdissect.so $objs

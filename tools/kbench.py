@@ -18,6 +18,57 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, ROOT)
 
 
+def timeline_report(key, buf, NW=16384):
+    """The per-wave stamps of one dissect_fast launch (KB_DBG) as text."""
+    a = buf.reshape(5, NW).astype(np.int64)
+    # the last launch's waves alone (an earlier launch on a larger grid leaves
+    # its stamps in the slots past this grid's): a launch lasts well under 1 ms
+    nw = int(np.count_nonzero(a[0] > a[0].max() - 100000))
+    assert np.all(a[0][:nw] > a[0].max() - 100000)
+    st, en, be, hw, t78 = (a[k][:nw] for k in range(5))
+    t0 = st.min()
+    us = lambda x: (x - t0) / 100.0   # noqa: E731
+    s, e, bl, m = us(st), us(en), us(be), us(t78)
+    xcc = hw & 15
+    hid = hw >> 8
+    cu = (xcc << 8) | (((hid >> 13) & 3) << 5) | (((hid >> 12) & 1) << 4) | ((hid >> 8) & 15)
+    grp = (np.arange(nw) // 4) % 8
+    wv = np.arange(nw) % 4
+    q = lambda x: " ".join(f"{np.percentile(x, p):.1f}" for p in (0, 10, 50, 90, 100))   # noqa: E731
+    L = [f"{key} waves {nw}, CUs {len(np.unique(cu))}, XCDs {len(np.unique(xcc))} (us from the first wave's start; p0 p10 p50 p90 p100)",
+         f"  wave start      {q(s)}",
+         f"  7/8 of share    {q(m[t78 > 0]) if (t78 > 0).any() else '-'}   ({int((t78 > 0).sum())} waves: the mark is a static tile's)",
+         f"  fast_tiles end  {q(e)}   mean {e.mean():.1f}",
+         f"  block end       {q(bl)}",
+         "  by XCD (XCC_ID): waves, fast_tiles end mean / max, block%8 labels seen"]
+    for x in np.unique(xcc):
+        k = xcc == x
+        L.append(f"    xcd {x}: {int(k.sum()):4d}  {e[k].mean():.1f} / {e[k].max():.1f}  labels {sorted(set(grp[k].tolist()))}")
+    cm = np.array([e[cu == c].mean() for c in np.unique(cu)])
+    cx = np.array([e[cu == c].max() for c in np.unique(cu)])
+    L.append(f"  by CU: mean end {q(cm)}; max end {q(cx)}; waves per CU {sorted(set(int((cu == c).sum()) for c in np.unique(cu)))}")
+    L.append(f"  by wave in block: mean end {[round(float(e[wv == w].mean()), 1) for w in range(4)]}")
+    blk = e[:nw - nw % 4].reshape(-1, 4)
+    L.append(f"  within-block spread mean {np.mean(blk.max(1) - blk.min(1)):.1f}, first / second half of the grid mean end "
+             f"{e[:nw // 2].mean():.1f} / {e[nw // 2:].mean():.1f}")
+    # a wave's pace before and after its 7/8 mark (us per 1/8 share): waves
+    # that speed up as others end would mean the tail is bandwidth-bound
+    ok = t78 > 0
+    if ok.sum() >= nw // 2:
+        front = (m[ok] - s[ok]) / 7.0
+        back = e[ok] - m[ok]
+        L.append(f"  us per eighth of a share: front {q(front)}; last eighth {q(back)}")
+        late = e[ok] >= np.percentile(e[ok], 90)
+        L.append(f"  the latest tenth of the waves: front {front[late].mean():.2f}, last eighth {back[late].mean():.2f}; "
+                 f"the earliest tenth: front {front[e[ok] <= np.percentile(e[ok], 10)].mean():.2f}, "
+                 f"last eighth {back[e[ok] <= np.percentile(e[ok], 10)].mean():.2f}")
+    # balanced end: the waves' tile phases at their own pace, work shared
+    # perfectly (the mean end), against the actual last end
+    L.append(f"  last fast_tiles end {e.max():.1f}, mean {e.mean():.1f}: a perfectly balanced tile phase would end "
+             f"{e.max() - e.mean():.1f} us ({100 * (e.max() - e.mean()) / bl.max():.1f} % of the launch) sooner at the waves' own pace")
+    return "\n".join(L)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", default="udp64,imix,ipv6x")
@@ -31,6 +82,8 @@ def main():
                     help="kernel schedule (nsd_set_schedule)")
     ap.add_argument("--bpf", action="store_true", help="also time the device BPF filter (bench.bpf_bench: "
                     "verdicts, and with the compaction, whose accepted count it checks)")
+    ap.add_argument("--dbg-out", default=os.path.join(ROOT, "bench_out", "var"),
+                    help="where KB_DBG keeps the stamps it read (dbg_<config>_rec<bytes>.npy)")
     ap.add_argument("--lib", default=None, help="a variant libnsdissect.so (tools/build_variant.sh) "
                     "loaded instead of the in-tree one (dev tools only; the product loads its own)")
     args = ap.parse_args()
@@ -72,25 +125,22 @@ def main():
                     print(f"{key:6s} per-group (block * 4 / grid: dispatch round) last tile-phase end {[us(int(x)) for x in c[40:48]]} "
                           f"last block end {[us(int(x)) for x in c[48:56]]}", flush=True)
             if os.environ.get("KB_DBG"):
-                # a variant with per-wave start / tile-phase end times (g_dbg,
-                # nsd_dbg_read): one more launch, then the spread within and
-                # across blocks
+                # a timing variant (tools/variants/timeline.patch: g_dbg,
+                # nsd_dbg_read) of dissect_fast: per wave, s_memrealtime at its
+                # start, one tile before 7/8 of its share, at the end of fast_tiles
+                # and at the block's end, and XCC_ID | HW_ID << 8.  One more
+                # launch, then the spread by XCD, CU and wave, and when a
+                # perfectly balanced launch would end.
                 import ctypes
                 b.step(args.mode, 0 if compact else args.grid, zero=False)
                 b.sync()
-                buf = np.zeros(3 * 16384, dtype=np.uint64)
+                NW = 16384
+                buf = np.zeros(5 * NW, dtype=np.uint64)
                 assert nsd.lib().nsd_dbg_read(ctypes.c_void_p(buf.ctypes.data)) == 0
-                st, en = buf[:16384].astype(np.int64), buf[16384:32768].astype(np.int64)
-                nw = int(np.count_nonzero(st))
-                st, en = st[:nw], en[:nw]
-                t = (en - st.min()) / 100.0
-                blk = t.reshape(-1, 4)
-                print(f"{key:6s} waves {nw}: tile-phase end us p0 {t.min():.1f} p10 {np.percentile(t, 10):.1f} "
-                      f"p50 {np.median(t):.1f} p90 {np.percentile(t, 90):.1f} p100 {t.max():.1f}; within-block "
-                      f"spread mean {np.mean(blk.max(1) - blk.min(1)):.1f}, block means' spread "
-                      f"{blk.mean(1).max() - blk.mean(1).min():.1f}; wave-in-block means "
-                      f"{[round(float(x), 1) for x in blk.mean(0)]}", flush=True)
-                np.save(os.path.join(ROOT, "gpurun_out", "var", f"dbg_{key}.npy"), buf)
+                out = args.dbg_out
+                os.makedirs(out, exist_ok=True)
+                np.save(os.path.join(out, f"dbg_{key}_rec{b.rec_b}.npy"), buf)
+                print(timeline_report(key, buf), flush=True)
             b.free()
             torch.cuda.empty_cache()
 
