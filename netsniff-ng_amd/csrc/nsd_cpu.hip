@@ -74,7 +74,7 @@ static void walk_packet(const uint8_t *pkt, uint32_t caplen, int start_id, const
 	walk_init(w, caplen, start_id);
 	if (start_id == NSD_OPS_SLL) {
 		// the SLL head pulls nothing and dispatches on pkt->sll (the device's
-		// sll_head, nsd_kernels.hip)
+		// sll_head, nsd_fused.h)
 		const uint32_t proto = sll ? __builtin_bswap16(sll->protocol) : 0u;
 		g.layer(w, 0, NSD_OPS_SLL, 0);
 		w.chain = NSD_OPS_SLL;

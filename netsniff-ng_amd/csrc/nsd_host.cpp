@@ -1,7 +1,8 @@
 // nsd_host.cpp - C ABI of the batch path (include/netsniff_dissect.h):
 // nsd_dissect_device[_ws|_sll] / dissector_entry_batch[_sll] launch the HIP
-// kernels of nsd_kernels.hip over a batch of frames.  There is no CPU walk
-// behind these entries: without a usable GPU they fail loudly (NSD_ERR_HIP).
+// kernels of nsd_kernels.hip (through their launcher, nsd_launch.hip) over a
+// batch of frames.  There is no CPU walk behind these entries: without a
+// usable GPU they fail loudly (NSD_ERR_HIP).
 // The reference's per-packet surface lives in nsd_proto.cpp.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -91,19 +92,29 @@ static int check_device_args(const uint8_t *d_frames, const nsd_desc_t *d_desc, 
 	return NSD_OK;
 }
 
+// The device entries' body: d_rec is n nsd_rec, or n nsd_crec when `compact`.
+static int dissect_device(const uint8_t *d_frames, const nsd_desc_t *d_desc, const nsd_sll_t *d_sll, uint32_t n,
+			  int linktype, int mode, void *d_rec, int compact, uint32_t *d_ext, uint32_t ext_cap,
+			  uint32_t *d_ext_count, uint64_t *d_counters, void *d_workspace, int grid, void *stream)
+{
+	if (n == 0)
+		return NSD_OK;
+	int rc = check_device_args(d_frames, d_desc, (const nsd_rec *)d_rec, d_ext, ext_cap, d_ext_count, d_counters,
+				   mode);
+	if (rc || !d_workspace)
+		return rc ? rc : NSD_ERR_ARG;
+	rc = nsd_launch_dissect_rec(d_frames, d_desc, d_sll, n, start_for(linktype), mode, d_rec, compact, d_ext,
+				    ext_cap, d_ext_count, d_counters, d_workspace, grid, (hipStream_t)stream);
+	return rc ? NSD_ERR_HIP : NSD_OK;
+}
+
 extern "C" int nsd_dissect_device_ws(const uint8_t *d_frames, const nsd_desc_t *d_desc, uint32_t n,
 				     int linktype, int mode, nsd_rec *d_rec, uint32_t *d_ext,
 				     uint32_t ext_cap, uint32_t *d_ext_count, uint64_t *d_counters,
 				     void *d_workspace, void *stream)
 {
-	if (n == 0)
-		return NSD_OK;
-	int rc = check_device_args(d_frames, d_desc, d_rec, d_ext, ext_cap, d_ext_count, d_counters, mode);
-	if (rc || !d_workspace)
-		return rc ? rc : NSD_ERR_ARG;
-	rc = nsd_launch_dissect(d_frames, d_desc, n, start_for(linktype), mode, d_rec, d_ext, ext_cap,
-				d_ext_count, d_counters, d_workspace, 0, (hipStream_t)stream);
-	return rc ? NSD_ERR_HIP : NSD_OK;
+	return dissect_device(d_frames, d_desc, nullptr, n, linktype, mode, d_rec, 0, d_ext, ext_cap, d_ext_count,
+			      d_counters, d_workspace, 0, stream);
 }
 
 // grid override for experiments (0 = default)
@@ -112,14 +123,8 @@ extern "C" int nsd_dissect_device_grid(const uint8_t *d_frames, const nsd_desc_t
 				       uint32_t *d_ext, uint32_t ext_cap, uint32_t *d_ext_count,
 				       uint64_t *d_counters, void *d_workspace, int grid, void *stream)
 {
-	if (n == 0)
-		return NSD_OK;
-	int rc = check_device_args(d_frames, d_desc, d_rec, d_ext, ext_cap, d_ext_count, d_counters, mode);
-	if (rc || !d_workspace)
-		return rc ? rc : NSD_ERR_ARG;
-	rc = nsd_launch_dissect(d_frames, d_desc, n, start_for(linktype), mode, d_rec, d_ext, ext_cap,
-				d_ext_count, d_counters, d_workspace, grid, (hipStream_t)stream);
-	return rc ? NSD_ERR_HIP : NSD_OK;
+	return dissect_device(d_frames, d_desc, nullptr, n, linktype, mode, d_rec, 0, d_ext, ext_cap, d_ext_count,
+			      d_counters, d_workspace, grid, stream);
 }
 
 // Without a caller workspace the library keeps one per process (allocated on
@@ -129,18 +134,17 @@ extern "C" int nsd_dissect_device(const uint8_t *d_frames, const nsd_desc_t *d_d
 				  uint32_t ext_cap, uint32_t *d_ext_count, uint64_t *d_counters,
 				  void *stream)
 {
+	// (nothing is allocated for a call that fails its checks)
 	if (n == 0)
 		return NSD_OK;
-	int rc = check_device_args(d_frames, d_desc, d_rec, d_ext, ext_cap, d_ext_count, d_counters, mode);
-	if (rc)
+	if (int rc = check_device_args(d_frames, d_desc, d_rec, d_ext, ext_cap, d_ext_count, d_counters, mode))
 		return rc;
 	DevCtx &c = g_ctx;
 	std::lock_guard<std::mutex> lk(c.mu);
 	if (!grow(c.dev_ws, c.dev_ws_cap, nsd_launch_workspace_bytes(n)))
 		return NSD_ERR_NOMEM;
-	rc = nsd_launch_dissect(d_frames, d_desc, n, start_for(linktype), mode, d_rec, d_ext, ext_cap,
-				d_ext_count, d_counters, c.dev_ws, 0, (hipStream_t)stream);
-	return rc ? NSD_ERR_HIP : NSD_OK;
+	return dissect_device(d_frames, d_desc, nullptr, n, linktype, mode, d_rec, 0, d_ext, ext_cap, d_ext_count,
+			      d_counters, c.dev_ws, 0, stream);
 }
 
 extern "C" int nsd_dissect_device_sll(const uint8_t *d_frames, const nsd_desc_t *d_desc,
@@ -149,14 +153,8 @@ extern "C" int nsd_dissect_device_sll(const uint8_t *d_frames, const nsd_desc_t 
 				      uint32_t *d_ext_count, uint64_t *d_counters, void *d_workspace,
 				      void *stream)
 {
-	if (n == 0)
-		return NSD_OK;
-	int rc = check_device_args(d_frames, d_desc, d_rec, d_ext, ext_cap, d_ext_count, d_counters, mode);
-	if (rc || !d_workspace)
-		return rc ? rc : NSD_ERR_ARG;
-	rc = nsd_launch_dissect_sll(d_frames, d_desc, d_sll, n, start_for(linktype), mode, d_rec, d_ext,
-				    ext_cap, d_ext_count, d_counters, d_workspace, 0, (hipStream_t)stream);
-	return rc ? NSD_ERR_HIP : NSD_OK;
+	return dissect_device(d_frames, d_desc, d_sll, n, linktype, mode, d_rec, 0, d_ext, ext_cap, d_ext_count,
+			      d_counters, d_workspace, 0, stream);
 }
 
 extern "C" int nsd_dissect_device_compact(const uint8_t *d_frames, const nsd_desc_t *d_desc,
@@ -165,15 +163,8 @@ extern "C" int nsd_dissect_device_compact(const uint8_t *d_frames, const nsd_des
 					  uint32_t *d_ext_used, uint64_t *d_counters, void *d_workspace,
 					  void *stream)
 {
-	if (n == 0)
-		return NSD_OK;
-	int rc = check_device_args(d_frames, d_desc, (const nsd_rec *)d_crec, d_ext, ext_words, d_ext_used,
-				   d_counters, mode);
-	if (rc || !d_workspace)
-		return rc ? rc : NSD_ERR_ARG;
-	rc = nsd_launch_dissect_rec(d_frames, d_desc, d_sll, n, start_for(linktype), mode, d_crec, 1, d_ext,
-				    ext_words, d_ext_used, d_counters, d_workspace, 0, (hipStream_t)stream);
-	return rc ? NSD_ERR_HIP : NSD_OK;
+	return dissect_device(d_frames, d_desc, d_sll, n, linktype, mode, d_crec, 1, d_ext, ext_words, d_ext_used,
+			      d_counters, d_workspace, 0, stream);
 }
 
 extern "C" int dissector_entry_batch(const uint8_t *frames, size_t frames_len,
@@ -219,7 +210,7 @@ extern "C" int dissector_entry_batch_sll(const uint8_t *frames, size_t frames_le
 		  hip_ok(hipMemsetAsync(c.ext_count, 0, 64 + NSD_NCOUNTERS * 8, s), "memset");
 	if (!ok)
 		return NSD_ERR_HIP;
-	if (nsd_launch_dissect_sll(c.frames, c.desc, sll ? c.sll : nullptr, n, start_for(linktype), mode, c.rec,
+	if (nsd_launch_dissect_rec(c.frames, c.desc, sll ? c.sll : nullptr, n, start_for(linktype), mode, c.rec, 0,
 				   ext_cap ? c.ext : nullptr, ext_cap, c.ext_count, c.counters, c.ws, 0, s))
 		return NSD_ERR_HIP;
 	uint32_t used = 0;

@@ -59,18 +59,11 @@ inline size_t batch_extent(const nsd_desc_t *desc, size_t n)
 	return used;
 }
 
-// ---- kernel launchers (nsd_kernels.hip) --------------------------------------
+// ---- the kernels' launcher (nsd_launch.hip) -----------------------------------
 // d_sll: one struct sockaddr_ll (nsd_sll_t, 20 bytes) per packet, or NULL
 // (read as zeros); d_rec: n nsd_rec (16 B), or n nsd_crec (8 B) when `compact`
 extern "C" int nsd_launch_dissect_rec(const uint8_t *d_frames, const uint64_t *d_desc, const void *d_sll,
 				      uint32_t n, int start_id, int mode, void *d_rec, int compact, uint32_t *d_ext,
-				      uint32_t ext_words, uint32_t *d_ext_used, uint64_t *d_counters, void *d_ws,
-				      int grid, hipStream_t stream);
-extern "C" int nsd_launch_dissect(const uint8_t *d_frames, const uint64_t *d_desc, uint32_t n, int start_id,
-				  int mode, nsd_rec *d_rec, uint32_t *d_ext, uint32_t ext_words, uint32_t *d_ext_used,
-				  uint64_t *d_counters, void *d_ws, int grid, hipStream_t stream);
-extern "C" int nsd_launch_dissect_sll(const uint8_t *d_frames, const uint64_t *d_desc, const void *d_sll,
-				      uint32_t n, int start_id, int mode, nsd_rec *d_rec, uint32_t *d_ext,
 				      uint32_t ext_words, uint32_t *d_ext_used, uint64_t *d_counters, void *d_ws,
 				      int grid, hipStream_t stream);
 extern "C" size_t nsd_launch_workspace_bytes(uint32_t n);

@@ -11,7 +11,7 @@
 // The byte source (Src) and the sink for what a layer records (Sink) are
 // template parameters, so the same layer step runs
 //   * on the device over an LDS-staged header window (the general walk of
-//     nsd_kernels.hip: wave-level sinks, ballots, LDS counters), and
+//     nsd_fused.h: wave-level sinks, ballots, LDS counters), and
 //   * on the host over the whole frame (nsd_cpu.hip: the per-packet entry
 //     point dissector_entry_point and the exported proto-ops objects, which
 //     SURVEY 8b keeps on the CPU: one packet per call is all launch latency).
@@ -361,7 +361,7 @@ NSD_HD int sll_next(uint32_t hatype, uint32_t proto, int mode, uint32_t e2)
 // (proto_ipv6_mobility_hdr.c:206-245), one byte per type
 #define NSD_MH_SUB 0x0A060612120A0A02ull
 
-// The general walk (the walkers of nsd_kernels.hip), one layer per call for
+// The general walk (the walkers of nsd_fused.h), one layer per call for
 // every lane of the wave:
 // dissector_main's loop body (dissector.c:51-58) for the ops `w.id`,
 // computed as straight-line selects over a per-ops rule table rather than a

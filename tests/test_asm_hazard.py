@@ -5,7 +5,7 @@ dwordx3 / dwordx4, and the 128-bit-data cmpswap_x2 atomics) reads its data
 VGPRs over two cycles: a VALU instruction that writes one of them within 2
 wait states of the store overwrites the data first.  hipcc pads its own
 stores; it does not know an inline-asm statement is such a store, so the
-split fast kernel's asm stores (nsd_kernels.hip st_b128 / put_rec_st) end
+split fast kernel's asm stores (nsd_stage.h st_b128 / put_rec_st) end
 in `s_nop 1` inside the string.  Without it a depth-3 build wrote corrupt
 list entries and faulted the GPU (round 3, commit 06a13b0).
 

@@ -703,7 +703,7 @@ def _cut_sweep(align=16):
     set to the cut, so the bytes right past caplen are exactly the headers a
     walk that ignored caplen would go on to parse.  The device's
     continuation windows are not zeroed past caplen and its 4-byte layer
-    reads do not mask them (nsd_kernels.hip LSrc::dword_at: every use is
+    reads do not mask them (nsd_stage.h LSrc::dword_at: every use is
     gated by the layer's pull); this is the test of that argument."""
     base = [p for p in edge_cases.cases() if 0 < len(p) <= 600]
     for cfg, n in ((T.SYN_IPV6X, 64), (T.SYN_IMIX, 32)):

@@ -85,6 +85,23 @@ def test_regions_disjoint_aligned_and_inside():
     assert shared > 1000
 
 
+def test_layout_values_pinned():
+    """The values themselves, not only their properties: the 20 words of every
+    (n, blocks, compact) of _sizes(), packed little-endian in enumeration
+    order, hash to what the launcher computed before the layout moved into
+    ws_layout (the kernels' pointer arguments are made of these numbers; a
+    change of the carve on purpose updates the digest)."""
+    import hashlib
+    import struct
+    ns, grids = _sizes()
+    h = hashlib.sha256()
+    for n in ns:
+        for want_blocks in grids:
+            for compact in (0, 1):
+                h.update(struct.pack("<20Q", *_layout(n, want_blocks, compact)))
+    assert h.hexdigest() == "ac033e87977b85cd4b2eff09eca903cd462a3b651b177f6eecff0be03053f89b"
+
+
 def test_shared_carve_fits_the_benchmark_shapes():
     """16M packets on 2 and 3 blocks per CU of 256 CUs: the shared tail's lists
     fit the bytes nsd_workspace_bytes returns (no growth)."""

@@ -24,7 +24,7 @@ used = torch.zeros(1, dtype=torch.int32, device=dev)
 cnt = torch.zeros(nsd.NCOUNTERS, dtype=torch.int64, device=dev)
 wsb = nsd.lib().nsd_workspace_bytes(n)
 ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-# gtiles at sched_pair_at(n) - NSD_MAX_GRID * 128 = wsb - 256 - 4096 * 128
+# gtiles at ws_layout's pair_at - NSD_MAX_GRID * 128 = wsb - 256 - 4096 * 128
 gt_off = wsb - 256 - 4096 * 128
 
 
