@@ -1,5 +1,5 @@
 // nsd_flow.h - the flow key of one dissected packet, shared by the device
-// kernels (nsd_flow.hip) and the host aggregation (nsd_flow_cpu).
+// kernels (nsd_flow.hip) and the host aggregation (nsd_flow_cpu.cpp).
 //
 // The reference shows per-flow packet and byte counters in flowtop
 // (flowtop.c: struct flow_entry's pkts_src / bytes_src, taken from

@@ -13,7 +13,9 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <algorithm>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/netsniff_dissect.h"
@@ -80,6 +82,40 @@ NSD_HIDDEN int nsd_start_for(int linktype);
 // than the current one (nsd_pipe.cpp)
 extern "C" NSD_HIDDEN int nsd_pipe_retarget(nsd_pipe *p, int linktype, int mode);
 
+// ---- the flow table (nsd_flow.hip) and its host form (nsd_flow_cpu.cpp) ----------
+// What both files agree on, host code: the limit of one update, which row
+// types carry times (the _ts forms' nsd_flowt / nsd_convt), the rows' orders.
+namespace nsdflow {
+constexpr uint32_t MAX_N = 0xFFFFFFF0u;   // the most packets of one update
+
+template <class Row>
+constexpr bool with_times()
+{
+	return std::is_same<Row, nsd_flowt>::value || std::is_same<Row, nsd_convt>::value;
+}
+
+template <class Row>
+static void sort_by_first(std::vector<Row> &v)
+{
+	std::sort(v.begin(), v.end(), [](const Row &a, const Row &b) { return a.first < b.first; });
+}
+
+// the total order of the header: `by`'s metric descending, then first ascending
+template <class Conv>
+static void sort_conv(std::vector<Conv> &v, int by)
+{
+	std::sort(v.begin(), v.end(), [by](const Conv &a, const Conv &b) {
+		if (by != NSD_CONV_BY_FIRST) {
+			const uint64_t ma = by == NSD_CONV_BY_BYTES ? a.bytes_src + a.bytes_dst : a.pkts_src + a.pkts_dst;
+			const uint64_t mb = by == NSD_CONV_BY_BYTES ? b.bytes_src + b.bytes_dst : b.pkts_src + b.pkts_dst;
+			if (ma != mb)
+				return ma > mb;
+		}
+		return a.first < b.first;
+	});
+}
+} // namespace nsdflow
+
 // the flow table's feeds of host batches (nsd_flow.hip).  ts: the packets'
 // timestamps, read for a timed table only (where it must be given); *ts_max
 // (may be NULL) is raised to the largest timestamp among the packets fed
@@ -91,8 +127,8 @@ extern "C" NSD_HIDDEN int nsd_flow_feed_records(nsd_flow_table *t, const uint8_t
 						const nsd_desc_t *desc, uint32_t n, const nsd_rec *rec,
 						const uint32_t *ext, uint32_t ext_words, const uint64_t *ts, uint64_t base);
 // nsd_flow_expire / nsd_flow_expire_ts with room for every flow: the removed
-// rows, sorted by `first`, into `rows` (nsd_flow.hip; the capture-file loop's,
-// nsd_replay.cpp)
+// rows, sorted by `first`, into `rows` (nsd_flow.hip, "expiry: the entries";
+// the capture-file loop's, nsd_replay.cpp)
 NSD_HIDDEN long nsd_flow_expire_rows(nsd_flow_table *t, uint64_t before, uint32_t flags, uint32_t max,
 				     std::vector<nsd_flow> &rows, uint64_t *stats);
 NSD_HIDDEN long nsd_flow_expire_rows_ts(nsd_flow_table *t, uint64_t before_ns, uint32_t flags, uint32_t max,

@@ -92,7 +92,7 @@ long read_big(nsd_pcap *p, const nsd_bpf_prog *filter, std::vector<uint8_t> &fra
 
 } // namespace
 
-// ---- flows of a capture file (nsd_flow.hip) -----------------------------------
+// ---- flows of a capture file (the table's feeds and entries: nsd_flow.hip) -------
 // read_pcap's loop (netsniff-ng.c:707-756: next record, bpf_run_filter, then
 // the dissector) with the flow table where the dissector's text would be:
 // batches of the reader go through the device filter / walk / update; a

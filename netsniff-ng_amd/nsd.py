@@ -806,74 +806,109 @@ class FlowTable:
         cuda tensor holding packet i's u64 timestamp (nsd_flow_update_device_ts;
         a timed table needs it, a plain one refuses it)."""
         n = desc.numel() if n is None else n
-        words = 0 if ext is None else ext.numel()
+        entry = "nsd_flow_update_device" if ts is None else "nsd_flow_update_device_ts"
+        args = [self.h, frames.data_ptr(), desc.data_ptr(), n, rec.data_ptr(), None if ext is None else ext.data_ptr(),
+                0 if ext is None else ext.numel()]
         if ts is not None:
-            rc = self.L.nsd_flow_update_device_ts(self.h, frames.data_ptr(), desc.data_ptr(), n, rec.data_ptr(),
-                                                  None if ext is None else ext.data_ptr(), words, ts.data_ptr(), base,
-                                                  self._stream(stream, desc.device))
-            _check(rc, "nsd_flow_update_device_ts")
-            return
-        rc = self.L.nsd_flow_update_device(self.h, frames.data_ptr(), desc.data_ptr(), n, rec.data_ptr(),
-                                           None if ext is None else ext.data_ptr(), words, base,
-                                           self._stream(stream, desc.device))
-        _check(rc, "nsd_flow_update_device")
+            args.append(ts.data_ptr())
+        _check(getattr(self.L, entry)(*args, base, self._stream(stream, desc.device)), entry)
 
-    def export_device(self, max_flows=None, flows=None, count=None, stats=None, stream=None):
-        """(flows u8[max*72], count i32[1], stats i64[8]) cuda tensors; count
-        may exceed max (only max rows are written), order unspecified."""
+    # Each entry has a plain and a _ts form (rows with t_first / t_last); the
+    # two methods of a pair call one body with the entry's name and its row dtype.
+    def _device_rows(self, rows, max_rows, dtype):
+        """The row tensor of a device entry and its capacity: u8[max * row size]."""
         import torch
-        if flows is None:
-            flows = torch.empty((self.slots if max_flows is None else max_flows) * FLOW_BYTES, dtype=torch.uint8,
-                                device="cuda")
-        if max_flows is None:
-            max_flows = flows.numel() // FLOW_BYTES
+        if rows is None:
+            rows = torch.empty((self.slots if max_rows is None else max_rows) * dtype.itemsize, dtype=torch.uint8,
+                               device="cuda")
+        return rows, rows.numel() // dtype.itemsize if max_rows is None else max_rows
+
+    def _host_rows(self, cap, dtype):
+        """(rows, stats) for a synchronous entry to fill."""
+        return np.zeros(max(cap, 1), dtype=dtype), np.zeros(FLOW_NSTATS, dtype=np.uint64)
+
+    def _export_device(self, entry, dtype, max_flows, flows, count, stats, stream):
+        import torch
+        flows, max_flows = self._device_rows(flows, max_flows, dtype)
         if count is None:
             count = torch.zeros(1, dtype=torch.int32, device=flows.device)
         if stats is None:
             stats = torch.zeros(FLOW_NSTATS, dtype=torch.int64, device=flows.device)
-        rc = self.L.nsd_flow_export_device(self.h, flows.data_ptr(), max_flows, count.data_ptr(), stats.data_ptr(),
-                                           self._stream(stream, flows.device))
-        _check(rc, "nsd_flow_export_device")
+        rc = getattr(self.L, entry)(self.h, flows.data_ptr(), max_flows, count.data_ptr(), stats.data_ptr(),
+                                    self._stream(stream, flows.device))
+        _check(rc, entry)
         return flows, count, stats
 
-    def export(self, max_flows=None):
-        """(flows FLOW_DTYPE sorted by `first`, stats u64[8]) in host memory;
-        synchronous."""
+    def _export(self, entry, dtype, max_flows):
         cap = self.slots if max_flows is None else max_flows
-        flows = np.zeros(max(cap, 1), dtype=FLOW_DTYPE)
-        stats = np.zeros(FLOW_NSTATS, dtype=np.uint64)
-        n = self.L.nsd_flow_export(self.h, flows.ctypes.data, cap, stats.ctypes.data)
-        _check(0 if n >= 0 else n, "nsd_flow_export")
+        flows, stats = self._host_rows(cap, dtype)
+        n = getattr(self.L, entry)(self.h, flows.ctypes.data, cap, stats.ctypes.data)
+        _check(0 if n >= 0 else n, entry)
         return flows[:min(n, cap)], stats
 
-    def conversations_device(self, by, k, conv=None, count=None, workspace=None, stream=None):
-        """The first k conversations of order `by` (nsd_flow_conv_device):
-        (conv u8[k*88], count i32[2] = rows written, conversations in the
-        table) cuda tensors; row order unspecified.  k = None: all."""
+    def _conversations_device(self, entry, dtype, by, k, conv, count, workspace, stream):
         import torch
         if k is None:
             k = 0xFFFFFFFF
         if conv is None:
-            conv = torch.empty(min(k, self.slots) * CONV_BYTES, dtype=torch.uint8, device="cuda")
+            conv = torch.empty(min(k, self.slots) * dtype.itemsize, dtype=torch.uint8, device="cuda")
         if count is None:
             count = torch.zeros(2, dtype=torch.int32, device=conv.device)
         if workspace is None:
             workspace = torch.empty(self.L.nsd_flow_conv_workspace_bytes(self.h), dtype=torch.uint8,
                                     device=conv.device)
-        rc = self.L.nsd_flow_conv_device(self.h, by, k, conv.data_ptr(), count.data_ptr(), workspace.data_ptr(),
-                                         self._stream(stream, conv.device))
-        _check(rc, "nsd_flow_conv_device")
+        rc = getattr(self.L, entry)(self.h, by, k, conv.data_ptr(), count.data_ptr(), workspace.data_ptr(),
+                                    self._stream(stream, conv.device))
+        _check(rc, entry)
         return conv, count
+
+    def _conversations(self, entry, dtype, by, k):
+        cap = self.slots if k is None else min(k, self.slots)
+        conv, stats = self._host_rows(cap, dtype)
+        n = getattr(self.L, entry)(self.h, by, cap, conv.ctypes.data, stats.ctypes.data)
+        _check(0 if n >= 0 else n, entry)
+        return conv[:min(n, cap)], stats
+
+    def _expire_device(self, entry, dtype, before, flags, max_flows, flows, count, workspace, stream):
+        import torch
+        flows, max_flows = self._device_rows(flows, max_flows, dtype)
+        if count is None:
+            count = torch.zeros(2, dtype=torch.int32, device=flows.device)
+        if workspace is None:
+            workspace = torch.empty(self.L.nsd_flow_expire_workspace_bytes(self.h), dtype=torch.uint8,
+                                    device=flows.device)
+        rc = getattr(self.L, entry)(self.h, before, flags, flows.data_ptr(), max_flows, count.data_ptr(),
+                                    workspace.data_ptr(), self._stream(stream, flows.device))
+        _check(rc, entry)
+        return flows, count
+
+    def _expire(self, entry, dtype, before, flags, max_flows):
+        cap = self.slots if max_flows is None else max_flows
+        flows, stats = self._host_rows(cap, dtype)
+        n = getattr(self.L, entry)(self.h, before, flags, flows.ctypes.data, cap, stats.ctypes.data)
+        _check(0 if n >= 0 else n, entry)
+        return flows[:min(n, cap)], n, stats
+
+    def export_device(self, max_flows=None, flows=None, count=None, stats=None, stream=None):
+        """(flows u8[max*72], count i32[1], stats i64[8]) cuda tensors; count
+        may exceed max (only max rows are written), order unspecified."""
+        return self._export_device("nsd_flow_export_device", FLOW_DTYPE, max_flows, flows, count, stats, stream)
+
+    def export(self, max_flows=None):
+        """(flows FLOW_DTYPE sorted by `first`, stats u64[8]) in host memory;
+        synchronous."""
+        return self._export("nsd_flow_export", FLOW_DTYPE, max_flows)
+
+    def conversations_device(self, by, k, conv=None, count=None, workspace=None, stream=None):
+        """The first k conversations of order `by` (nsd_flow_conv_device):
+        (conv u8[k*88], count i32[2] = rows written, conversations in the
+        table) cuda tensors; row order unspecified.  k = None: all."""
+        return self._conversations_device("nsd_flow_conv_device", CONV_DTYPE, by, k, conv, count, workspace, stream)
 
     def conversations(self, by=CONV_BY_BYTES, k=None):
         """(conv CONV_DTYPE, the first k of order `by`, in order; stats
         u64[8]) in host memory (nsd_flow_conversations); synchronous."""
-        cap = self.slots if k is None else min(k, self.slots)
-        conv = np.zeros(max(cap, 1), dtype=CONV_DTYPE)
-        stats = np.zeros(FLOW_NSTATS, dtype=np.uint64)
-        n = self.L.nsd_flow_conversations(self.h, by, cap, conv.ctypes.data, stats.ctypes.data)
-        _check(0 if n >= 0 else n, "nsd_flow_conversations")
-        return conv[:min(n, cap)], stats
+        return self._conversations("nsd_flow_conversations", CONV_DTYPE, by, k)
 
     def expire_device(self, before, flags=0, max_flows=None, flows=None, count=None, workspace=None, stream=None):
         """The flows with last < before leave the table as rows
@@ -881,114 +916,43 @@ class FlowTable:
         leaves only when both directions are idle): (flows u8[max*72], count
         i32[2] = rows written = flows removed, flows that qualified) cuda
         tensors; row order unspecified.  max_flows = None: room for all."""
-        import torch
-        if flows is None:
-            flows = torch.empty((self.slots if max_flows is None else max_flows) * FLOW_BYTES, dtype=torch.uint8,
-                                device="cuda")
-        if max_flows is None:
-            max_flows = flows.numel() // FLOW_BYTES
-        if count is None:
-            count = torch.zeros(2, dtype=torch.int32, device=flows.device)
-        if workspace is None:
-            workspace = torch.empty(self.L.nsd_flow_expire_workspace_bytes(self.h), dtype=torch.uint8,
-                                    device=flows.device)
-        rc = self.L.nsd_flow_expire_device(self.h, before, flags, flows.data_ptr(), max_flows, count.data_ptr(),
-                                           workspace.data_ptr(), self._stream(stream, flows.device))
-        _check(rc, "nsd_flow_expire_device")
-        return flows, count
+        return self._expire_device("nsd_flow_expire_device", FLOW_DTYPE, before, flags, max_flows, flows, count,
+                                   workspace, stream)
 
     def expire(self, before, flags=0, max_flows=None):
         """(removed flows FLOW_DTYPE sorted by `first`, the number that
         qualified, stats u64[8] after the call) in host memory
         (nsd_flow_expire); synchronous."""
-        cap = self.slots if max_flows is None else max_flows
-        flows = np.zeros(max(cap, 1), dtype=FLOW_DTYPE)
-        stats = np.zeros(FLOW_NSTATS, dtype=np.uint64)
-        n = self.L.nsd_flow_expire(self.h, before, flags, flows.ctypes.data, cap, stats.ctypes.data)
-        _check(0 if n >= 0 else n, "nsd_flow_expire")
-        return flows[:min(n, cap)], n, stats
+        return self._expire("nsd_flow_expire", FLOW_DTYPE, before, flags, max_flows)
 
     # ---- the same with times (a timed table; NsdError on a plain one) ----
     def export_device_ts(self, max_flows=None, flows=None, count=None, stats=None, stream=None):
         """export_device with FLOWT_DTYPE rows (flows u8[max*88])."""
-        import torch
-        if flows is None:
-            flows = torch.empty((self.slots if max_flows is None else max_flows) * FLOWT_BYTES, dtype=torch.uint8,
-                                device="cuda")
-        if max_flows is None:
-            max_flows = flows.numel() // FLOWT_BYTES
-        if count is None:
-            count = torch.zeros(1, dtype=torch.int32, device=flows.device)
-        if stats is None:
-            stats = torch.zeros(FLOW_NSTATS, dtype=torch.int64, device=flows.device)
-        rc = self.L.nsd_flow_export_device_ts(self.h, flows.data_ptr(), max_flows, count.data_ptr(), stats.data_ptr(),
-                                              self._stream(stream, flows.device))
-        _check(rc, "nsd_flow_export_device_ts")
-        return flows, count, stats
+        return self._export_device("nsd_flow_export_device_ts", FLOWT_DTYPE, max_flows, flows, count, stats, stream)
 
     def export_ts(self, max_flows=None):
         """export with FLOWT_DTYPE rows."""
-        cap = self.slots if max_flows is None else max_flows
-        flows = np.zeros(max(cap, 1), dtype=FLOWT_DTYPE)
-        stats = np.zeros(FLOW_NSTATS, dtype=np.uint64)
-        n = self.L.nsd_flow_export_ts(self.h, flows.ctypes.data, cap, stats.ctypes.data)
-        _check(0 if n >= 0 else n, "nsd_flow_export_ts")
-        return flows[:min(n, cap)], stats
+        return self._export("nsd_flow_export_ts", FLOWT_DTYPE, max_flows)
 
     def conversations_device_ts(self, by, k, conv=None, count=None, workspace=None, stream=None):
         """conversations_device with CONVT_DTYPE rows (conv u8[k*104])."""
-        import torch
-        if k is None:
-            k = 0xFFFFFFFF
-        if conv is None:
-            conv = torch.empty(min(k, self.slots) * CONVT_BYTES, dtype=torch.uint8, device="cuda")
-        if count is None:
-            count = torch.zeros(2, dtype=torch.int32, device=conv.device)
-        if workspace is None:
-            workspace = torch.empty(self.L.nsd_flow_conv_workspace_bytes(self.h), dtype=torch.uint8,
-                                    device=conv.device)
-        rc = self.L.nsd_flow_conv_device_ts(self.h, by, k, conv.data_ptr(), count.data_ptr(), workspace.data_ptr(),
-                                            self._stream(stream, conv.device))
-        _check(rc, "nsd_flow_conv_device_ts")
-        return conv, count
+        return self._conversations_device("nsd_flow_conv_device_ts", CONVT_DTYPE, by, k, conv, count, workspace,
+                                          stream)
 
     def conversations_ts(self, by=CONV_BY_BYTES, k=None):
         """conversations with CONVT_DTYPE rows."""
-        cap = self.slots if k is None else min(k, self.slots)
-        conv = np.zeros(max(cap, 1), dtype=CONVT_DTYPE)
-        stats = np.zeros(FLOW_NSTATS, dtype=np.uint64)
-        n = self.L.nsd_flow_conversations_ts(self.h, by, cap, conv.ctypes.data, stats.ctypes.data)
-        _check(0 if n >= 0 else n, "nsd_flow_conversations_ts")
-        return conv[:min(n, cap)], stats
+        return self._conversations("nsd_flow_conversations_ts", CONVT_DTYPE, by, k)
 
     def expire_device_ts(self, before_ns, flags=0, max_flows=None, flows=None, count=None, workspace=None,
                          stream=None):
         """expire_device by time: the flows with t_last < before_ns leave as
         FLOWT_DTYPE rows (flows u8[max*88])."""
-        import torch
-        if flows is None:
-            flows = torch.empty((self.slots if max_flows is None else max_flows) * FLOWT_BYTES, dtype=torch.uint8,
-                                device="cuda")
-        if max_flows is None:
-            max_flows = flows.numel() // FLOWT_BYTES
-        if count is None:
-            count = torch.zeros(2, dtype=torch.int32, device=flows.device)
-        if workspace is None:
-            workspace = torch.empty(self.L.nsd_flow_expire_workspace_bytes(self.h), dtype=torch.uint8,
-                                    device=flows.device)
-        rc = self.L.nsd_flow_expire_device_ts(self.h, before_ns, flags, flows.data_ptr(), max_flows, count.data_ptr(),
-                                              workspace.data_ptr(), self._stream(stream, flows.device))
-        _check(rc, "nsd_flow_expire_device_ts")
-        return flows, count
+        return self._expire_device("nsd_flow_expire_device_ts", FLOWT_DTYPE, before_ns, flags, max_flows, flows,
+                                   count, workspace, stream)
 
     def expire_ts(self, before_ns, flags=0, max_flows=None):
         """expire by time, FLOWT_DTYPE rows."""
-        cap = self.slots if max_flows is None else max_flows
-        flows = np.zeros(max(cap, 1), dtype=FLOWT_DTYPE)
-        stats = np.zeros(FLOW_NSTATS, dtype=np.uint64)
-        n = self.L.nsd_flow_expire_ts(self.h, before_ns, flags, flows.ctypes.data, cap, stats.ctypes.data)
-        _check(0 if n >= 0 else n, "nsd_flow_expire_ts")
-        return flows[:min(n, cap)], n, stats
+        return self._expire("nsd_flow_expire_ts", FLOWT_DTYPE, before_ns, flags, max_flows)
 
     def close(self):
         if getattr(self, "h", None):
@@ -1013,77 +977,60 @@ def flow_batch(frames, desc, mode=PRINT_NORM, linktype=LINKTYPE_EN10MB, max_flow
     return flows[:min(n, cap)], stats
 
 
-def flow_cpu(frames, desc, rec, ext=None, base=0, max_flows=None):
-    """The flow aggregation on the host CPU (nsd_flow_cpu) over records
-    already made (REC_DTYPE, ext = the u32 pool their slots index): (flows
-    FLOW_DTYPE sorted by `first`, stats u64[8])."""
+# The host forms come in the same pairs as FlowTable's methods: each pair
+# calls one body with the entry's name and its row dtype.
+def _flow_cpu(entry, dtype, frames, desc, rec, ts, ext, base, max_flows):
     frames = np.ascontiguousarray(frames, dtype=np.uint8)
     desc = np.ascontiguousarray(desc, dtype=np.uint64)
     rec = np.ascontiguousarray(rec, dtype=REC_DTYPE)
     ext_keep = None if ext is None or len(ext) == 0 else np.ascontiguousarray(ext).view(np.uint32)
+    args = [frames.ctypes.data, desc.ctypes.data, len(desc), rec.ctypes.data,
+            None if ext_keep is None else ext_keep.ctypes.data]
+    if dtype is FLOWT_DTYPE:
+        ts = np.ascontiguousarray(ts, dtype=np.uint64)
+        if len(ts) != len(desc):
+            raise ValueError("one timestamp per packet")
+        args.append(ts.ctypes.data)
     cap = len(desc) if max_flows is None else max_flows
-    flows = np.zeros(max(cap, 1), dtype=FLOW_DTYPE)
+    flows = np.zeros(max(cap, 1), dtype=dtype)
     stats = np.zeros(FLOW_NSTATS, dtype=np.uint64)
-    n = lib().nsd_flow_cpu(frames.ctypes.data, desc.ctypes.data, len(desc), rec.ctypes.data,
-                           None if ext_keep is None else ext_keep.ctypes.data, base, flows.ctypes.data, cap,
-                           stats.ctypes.data)
-    _check(0 if n >= 0 else n, "nsd_flow_cpu")
+    n = getattr(lib(), entry)(*args, base, flows.ctypes.data, cap, stats.ctypes.data)
+    _check(0 if n >= 0 else n, entry)
     return flows[:min(n, cap)], stats
+
+
+def flow_cpu(frames, desc, rec, ext=None, base=0, max_flows=None):
+    """The flow aggregation on the host CPU (nsd_flow_cpu) over records
+    already made (REC_DTYPE, ext = the u32 pool their slots index): (flows
+    FLOW_DTYPE sorted by `first`, stats u64[8])."""
+    return _flow_cpu("nsd_flow_cpu", FLOW_DTYPE, frames, desc, rec, None, ext, base, max_flows)
 
 
 def flow_cpu_ts(frames, desc, rec, ts, ext=None, base=0, max_flows=None):
     """flow_cpu with ts[n], the packets' u64 timestamps (nsd_flow_cpu_ts):
     (flows FLOWT_DTYPE sorted by `first`, stats u64[8])."""
-    frames = np.ascontiguousarray(frames, dtype=np.uint8)
-    desc = np.ascontiguousarray(desc, dtype=np.uint64)
-    rec = np.ascontiguousarray(rec, dtype=REC_DTYPE)
-    ts = np.ascontiguousarray(ts, dtype=np.uint64)
-    if len(ts) != len(desc):
-        raise ValueError("one timestamp per packet")
-    ext_keep = None if ext is None or len(ext) == 0 else np.ascontiguousarray(ext).view(np.uint32)
-    cap = len(desc) if max_flows is None else max_flows
-    flows = np.zeros(max(cap, 1), dtype=FLOWT_DTYPE)
-    stats = np.zeros(FLOW_NSTATS, dtype=np.uint64)
-    n = lib().nsd_flow_cpu_ts(frames.ctypes.data, desc.ctypes.data, len(desc), rec.ctypes.data,
-                              None if ext_keep is None else ext_keep.ctypes.data, ts.ctypes.data, base,
-                              flows.ctypes.data, cap, stats.ctypes.data)
-    _check(0 if n >= 0 else n, "nsd_flow_cpu_ts")
-    return flows[:min(n, cap)], stats
+    return _flow_cpu("nsd_flow_cpu_ts", FLOWT_DTYPE, frames, desc, rec, ts, ext, base, max_flows)
 
 
-def conv_cpu_ts(flows, by=CONV_BY_FIRST, max_conv=None):
-    """conv_cpu over FLOWT_DTYPE rows (nsd_conv_cpu_ts): CONVT_DTYPE rows,
-    t_first / t_last = min / max over both directions."""
-    flows = np.ascontiguousarray(flows, dtype=FLOWT_DTYPE)
+def _conv_cpu(entry, flow_dtype, conv_dtype, flows, by, max_conv):
+    flows = np.ascontiguousarray(flows, dtype=flow_dtype)
     cap = len(flows) if max_conv is None else max_conv
-    conv = np.zeros(max(cap, 1), dtype=CONVT_DTYPE)
-    n = lib().nsd_conv_cpu_ts(flows.ctypes.data, len(flows), by, conv.ctypes.data, cap)
-    _check(0 if n >= 0 else n, "nsd_conv_cpu_ts")
+    conv = np.zeros(max(cap, 1), dtype=conv_dtype)
+    n = getattr(lib(), entry)(flows.ctypes.data, len(flows), by, conv.ctypes.data, cap)
+    _check(0 if n >= 0 else n, entry)
     return conv[:min(n, cap)]
-
-
-def flow_expire_cpu_ts(flows, before_ns, flags=0, max_flows=None):
-    """flow_expire_cpu by time over FLOWT_DTYPE rows (nsd_flow_expire_cpu_ts):
-    a row qualifies when its t_last < before_ns."""
-    rest = np.array(flows, dtype=FLOWT_DTYPE, ndmin=1)     # (a copy: the call compacts it)
-    cap = len(rest) if max_flows is None else max_flows
-    expired = np.zeros(max(cap, 1), dtype=FLOWT_DTYPE)
-    remaining = ctypes.c_size_t(0)
-    n = lib().nsd_flow_expire_cpu_ts(rest.ctypes.data, len(rest), before_ns, flags, expired.ctypes.data, cap,
-                                     ctypes.byref(remaining))
-    _check(0 if n >= 0 else n, "nsd_flow_expire_cpu_ts")
-    return rest[:remaining.value], expired[:min(n, cap)], n
 
 
 def conv_cpu(flows, by=CONV_BY_FIRST, max_conv=None):
     """Flow rows (FLOW_DTYPE, any order, unique keys) paired into
     conversations on the host CPU (nsd_conv_cpu): CONV_DTYPE in order `by`."""
-    flows = np.ascontiguousarray(flows, dtype=FLOW_DTYPE)
-    cap = len(flows) if max_conv is None else max_conv
-    conv = np.zeros(max(cap, 1), dtype=CONV_DTYPE)
-    n = lib().nsd_conv_cpu(flows.ctypes.data, len(flows), by, conv.ctypes.data, cap)
-    _check(0 if n >= 0 else n, "nsd_conv_cpu")
-    return conv[:min(n, cap)]
+    return _conv_cpu("nsd_conv_cpu", FLOW_DTYPE, CONV_DTYPE, flows, by, max_conv)
+
+
+def conv_cpu_ts(flows, by=CONV_BY_FIRST, max_conv=None):
+    """conv_cpu over FLOWT_DTYPE rows (nsd_conv_cpu_ts): CONVT_DTYPE rows,
+    t_first / t_last = min / max over both directions."""
+    return _conv_cpu("nsd_conv_cpu_ts", FLOWT_DTYPE, CONVT_DTYPE, flows, by, max_conv)
 
 
 def pcap_flows(path, table, mode=PRINT_NORM, prog=None):
@@ -1095,19 +1042,44 @@ def pcap_flows(path, table, mode=PRINT_NORM, prog=None):
     return n
 
 
+def _flow_expire_cpu(entry, dtype, flows, before, flags, max_flows):
+    rest = np.array(flows, dtype=dtype, ndmin=1)     # (a copy: the call compacts it)
+    cap = len(rest) if max_flows is None else max_flows
+    expired = np.zeros(max(cap, 1), dtype=dtype)
+    remaining = ctypes.c_size_t(0)
+    n = getattr(lib(), entry)(rest.ctypes.data, len(rest), before, flags, expired.ctypes.data, cap,
+                              ctypes.byref(remaining))
+    _check(0 if n >= 0 else n, entry)
+    return rest[:remaining.value], expired[:min(n, cap)], n
+
+
 def flow_expire_cpu(flows, before, flags=0, max_flows=None):
     """The expiry rules on the host CPU (nsd_flow_expire_cpu) over flow rows
     (FLOW_DTYPE, unique keys): (remaining rows in their input order, expired
     rows = the first max_flows qualifying ones in input order, the number
     that qualified)."""
-    rest = np.array(flows, dtype=FLOW_DTYPE, ndmin=1)     # (a copy: the call compacts it)
-    cap = len(rest) if max_flows is None else max_flows
-    expired = np.zeros(max(cap, 1), dtype=FLOW_DTYPE)
-    remaining = ctypes.c_size_t(0)
-    n = lib().nsd_flow_expire_cpu(rest.ctypes.data, len(rest), before, flags, expired.ctypes.data, cap,
-                                  ctypes.byref(remaining))
-    _check(0 if n >= 0 else n, "nsd_flow_expire_cpu")
-    return rest[:remaining.value], expired[:min(n, cap)], n
+    return _flow_expire_cpu("nsd_flow_expire_cpu", FLOW_DTYPE, flows, before, flags, max_flows)
+
+
+def flow_expire_cpu_ts(flows, before_ns, flags=0, max_flows=None):
+    """flow_expire_cpu by time over FLOWT_DTYPE rows (nsd_flow_expire_cpu_ts):
+    a row qualifies when its t_last < before_ns."""
+    return _flow_expire_cpu("nsd_flow_expire_cpu_ts", FLOWT_DTYPE, flows, before_ns, flags, max_flows)
+
+
+def _pcap_flows_expire(entry, dtype, path, table, every, idle, flags, mode, prog):
+    calls = []
+
+    @FLOW_SINK
+    def sink(rows, n, user):
+        buf = ctypes.string_at(rows, n * dtype.itemsize)
+        calls.append(np.frombuffer(buf, dtype=dtype).copy())
+        return 0
+
+    n = getattr(lib(), entry)(os.fsencode(path), mode, prog.h if prog is not None else None, table.h, every, idle,
+                              flags, sink, None)
+    _check(0 if n >= 0 else n, entry)
+    return n, calls
 
 
 def pcap_flows_expire(path, table, every, idle, flags=0, mode=PRINT_NORM, prog=None):
@@ -1117,18 +1089,7 @@ def pcap_flows_expire(path, table, every, idle, flags=0, mode=PRINT_NORM, prog=N
     `idle` packets back leave.  Returns (packets fed, [FLOW_DTYPE rows of each
     expiry that removed any, sorted by `first`]); the flows still in the table
     stay there for table.export()."""
-    calls = []
-
-    @FLOW_SINK
-    def sink(rows, n, user):
-        buf = ctypes.string_at(rows, n * FLOW_BYTES)
-        calls.append(np.frombuffer(buf, dtype=FLOW_DTYPE).copy())
-        return 0
-
-    n = lib().nsd_pcap_flows_expire(os.fsencode(path), mode, prog.h if prog is not None else None, table.h, every, idle,
-                                    flags, sink, None)
-    _check(0 if n >= 0 else n, "nsd_pcap_flows_expire")
-    return n, calls
+    return _pcap_flows_expire("nsd_pcap_flows_expire", FLOW_DTYPE, path, table, every, idle, flags, mode, prog)
 
 
 def pcap_flows_expire_ts(path, table, every, idle_ns, flags=0, mode=PRINT_NORM, prog=None):
@@ -1137,18 +1098,7 @@ def pcap_flows_expire_ts(path, table, every, idle_ns, flags=0, mode=PRINT_NORM, 
     fed exceeds idle_ns, the flows whose t_last lies more than idle_ns before
     it leave.  Returns (packets fed, [FLOWT_DTYPE rows of each expiry that
     removed any, sorted by `first`])."""
-    calls = []
-
-    @FLOW_SINK
-    def sink(rows, n, user):
-        buf = ctypes.string_at(rows, n * FLOWT_BYTES)
-        calls.append(np.frombuffer(buf, dtype=FLOWT_DTYPE).copy())
-        return 0
-
-    n = lib().nsd_pcap_flows_expire_ts(os.fsencode(path), mode, prog.h if prog is not None else None, table.h, every,
-                                       idle_ns, flags, sink, None)
-    _check(0 if n >= 0 else n, "nsd_pcap_flows_expire_ts")
-    return n, calls
+    return _pcap_flows_expire("nsd_pcap_flows_expire_ts", FLOWT_DTYPE, path, table, every, idle_ns, flags, mode, prog)
 
 
 # ---- pcap replay front end (nsd_pcap.cpp the reader, nsd_replay.cpp the replay) ---------------------------------------

@@ -143,3 +143,53 @@ def test_wrap_basics():
     s = b"\033[1m" + b"y" * 90 + b"\033[0m\n"
     out, _ = nsd.tprintf_wrap(s, cols=80)
     assert out.count(b"\n   ") == 1
+
+
+# The flow table's Python front end as callers know it: every public FlowTable
+# method and the module functions beside it, with the parameters and defaults
+# of commit 93356fb (before the plain / _ts pairs were folded into shared
+# bodies).  Literal strings on purpose: nothing here is read from nsd.py.
+_FLOWTABLE_SIGNATURES = {
+    "__init__": "(self, max_flows, timed=False)",
+    "close": "(self)",
+    "conversations": "(self, by=1, k=None)",
+    "conversations_device": "(self, by, k, conv=None, count=None, workspace=None, stream=None)",
+    "conversations_device_ts": "(self, by, k, conv=None, count=None, workspace=None, stream=None)",
+    "conversations_ts": "(self, by=1, k=None)",
+    "expire": "(self, before, flags=0, max_flows=None)",
+    "expire_device": "(self, before, flags=0, max_flows=None, flows=None, count=None, workspace=None, stream=None)",
+    "expire_device_ts": "(self, before_ns, flags=0, max_flows=None, flows=None, count=None, workspace=None, stream=None)",
+    "expire_ts": "(self, before_ns, flags=0, max_flows=None)",
+    "export": "(self, max_flows=None)",
+    "export_device": "(self, max_flows=None, flows=None, count=None, stats=None, stream=None)",
+    "export_device_ts": "(self, max_flows=None, flows=None, count=None, stats=None, stream=None)",
+    "export_ts": "(self, max_flows=None)",
+    "reset": "(self, stream=None)",
+    "update": "(self, frames, desc, rec, ext=None, base=0, n=None, stream=None, ts=None)",
+}
+_FLOW_FUNCTION_SIGNATURES = {
+    "flow_batch": "(frames, desc, mode=0, linktype=1, max_flows=None)",
+    "flow_cpu": "(frames, desc, rec, ext=None, base=0, max_flows=None)",
+    "flow_cpu_ts": "(frames, desc, rec, ts, ext=None, base=0, max_flows=None)",
+    "conv_cpu": "(flows, by=0, max_conv=None)",
+    "conv_cpu_ts": "(flows, by=0, max_conv=None)",
+    "flow_expire_cpu": "(flows, before, flags=0, max_flows=None)",
+    "flow_expire_cpu_ts": "(flows, before_ns, flags=0, max_flows=None)",
+    "pcap_flows": "(path, table, mode=0, prog=None)",
+    "pcap_flows_expire": "(path, table, every, idle, flags=0, mode=0, prog=None)",
+    "pcap_flows_expire_ts": "(path, table, every, idle_ns, flags=0, mode=0, prog=None)",
+}
+
+
+def test_flow_front_end_signatures_pinned():
+    import inspect
+    public = {name for name, member in vars(nsd.FlowTable).items()
+              if callable(member) and (not name.startswith("_") or name == "__init__")}
+    assert public == set(_FLOWTABLE_SIGNATURES)
+    for name, sig in _FLOWTABLE_SIGNATURES.items():
+        assert str(inspect.signature(getattr(nsd.FlowTable, name))) == sig, name
+    for name, sig in _FLOW_FUNCTION_SIGNATURES.items():
+        assert str(inspect.signature(getattr(nsd, name))) == sig, name
+    # the row sizes the folded bodies take from the dtypes are the ABI's
+    assert (nsd.FLOW_DTYPE.itemsize, nsd.FLOWT_DTYPE.itemsize) == (nsd.FLOW_BYTES, nsd.FLOWT_BYTES) == (72, 88)
+    assert (nsd.CONV_DTYPE.itemsize, nsd.CONVT_DTYPE.itemsize) == (nsd.CONV_BYTES, nsd.CONVT_BYTES) == (88, 104)

@@ -12,9 +12,9 @@ bytes (no code shared with the product); rows and all eight stats compare
 exactly.  A census over the oracle's records keeps the corpora from going
 bland: each test asserts that its corpus still holds the cases it is for.
 
-CPU tests run nsd_flow_cpu (the host form of the shared key function); GPU
-tests run the device walk and the update kernels (plain and timed) and export
-through poisoned buffers.
+CPU tests run nsd_flow_cpu (nsd_flow_cpu.cpp, the host form of the shared key
+function); GPU tests run the device walk and the update kernels (plain and
+timed, nsd_flow_table.h) and export through poisoned buffers.
 """
 import numpy as np
 import pytest

@@ -35,7 +35,7 @@ if [ -f $d/x/a/csrc/nsd_launch.hip ]; then
   $H -c $d/x/a/csrc/nsd_launch.hip -o $d/l.o
   objs="$objs $d/l.o"
 fi
-for f in nsd_bpf nsd_cpu nsd_host nsd_pipe nsd_format nsd_lookup nsd_pcap nsd_replay nsd_proto nsd_flow; do
+for f in nsd_bpf nsd_cpu nsd_host nsd_pipe nsd_format nsd_lookup nsd_pcap nsd_replay nsd_proto nsd_flow nsd_flow_cpu; do
   objs="$objs netsniff-ng_amd/build/$f.o"
 done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $d/libnsdissect.so $objs
